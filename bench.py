@@ -23,9 +23,14 @@ its slice and copies it into one pinned host model) and ``fedopt_waves`` (BASELI
 1 B bf16 params x 128 FedYogi updates streamed from pinned host memory in waves, sliced over the
 N GPUs of one process, each over its own PCIe link; fedn_amd/waves.py).
 
-Also measured in the same run:
+A plain run (no --full) sets up the seeded inputs, warms up, times --steps steps, writes the last
+step's result if --dump-outputs DIR is given and prints the line: the headline fields, ``config``,
+``throughput`` and, at N = 1, ``roofline`` from the HIP events of the timed steps themselves. Every
+"beside" field named above and everything below takes work of its own and runs only with --full.
+
+With --full, also measured in the same run:
   roofline      algorithmic bytes of the fold (K*P*4 + P*4 per launch at N = 1; per rank and
-                step at N > 1) / its kernel time (HIP events on the launch stream) vs the
+                step at N > 1, where its fold-only timing is a run of its own: --full only) / its kernel time (HIP events on the launch stream) vs the
                 8.0 TB/s HBM3E peak; ``traffic`` = HBM bytes per launch from rocprofv3 PMC
                 counters (profiles/pmc_traffic.json, collected by tools/gpu_session.sh pmc + tools/pmc_traffic.py --session) when
                 that entry was measured on the libfedagg.so this run loads (its sha256), else
@@ -98,6 +103,13 @@ def parse():
     ap.add_argument("--host-clients", type=int, default=16,
                     help="host_resident side field: host numpy updates through the plug-in (0 = skip)")
     ap.add_argument("--launch-check", action="store_true", help="rank set-up only (gloo, no GPU): the launcher's test")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: the CPU baseline and oracle checks, the roofline runs of their own "
+                         "and every side field (off by default: a plain run sets up, warms up, times --steps steps and "
+                         "prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the aggregated model, or a "
+                         "fixed seeded sample of it above DUMP_MAX_ELEMS values) as DIR/<name>.npy (float32)")
     return ap.parse_args()
 
 
@@ -122,6 +134,27 @@ def make_updates(K, P, dtype, device, seed):
     del base
     torch.cuda.synchronize(device)
     return ups
+
+
+DUMP_MAX_ELEMS = 12 << 20     # float32 values per dumped array (48 MiB; the whole dump stays under 64 MB)
+DUMP_EDGE = 1 << 20           # of a sampled array: this many leading and trailing values are kept whole
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each named result of the last timed step as ``dirname/<name>.npy`` (float32).
+    An array above DUMP_MAX_ELEMS values is written as a fixed sample: its first and last DUMP_EDGE values
+    and, between them, values at positions drawn once from a fixed seed (sorted; the same positions for the
+    same length, whatever the build or the run)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            mid = np.sort(np.random.default_rng(20261019).integers(DUMP_EDGE, n - DUMP_EDGE,
+                                                                   DUMP_MAX_ELEMS - 2 * DUMP_EDGE))
+            idx = torch.from_numpy(mid).to(t.device)
+            t = torch.cat([t[:DUMP_EDGE], t[idx], t[n - DUMP_EDGE:]])
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def file_sha(path):
@@ -851,6 +884,8 @@ def main():
         for _ in range(a.warmup):
             step()
         elapsed, kern_ms = timed_steps(step, a.steps, stream, world, device, rehearsal)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"aggregate": agg})
         alg_bytes = K * P * in_bytes + P * 4           # read every update once, write the aggregate once
         workload = f"fedavg_k{K}_p{P}_{a.dtype}"
         kernel = fold_kernel_label(P, in_bytes, K)
@@ -859,7 +894,7 @@ def main():
                   "clients": K, "params_per_gpu": P, "global_params": P_total,
                   "parallelism": "param-slice shards x1, no data-path collective"}
         scaling = "weak"
-        if rank == 0 and S:
+        if a.full and rank == 0 and S:
             base = cpu_baseline(ups, ns, agg, S)
     else:
         # the fold + gather step: rounds R (--ag-rounds, or the fastest of AG_ROUNDS) and transport
@@ -963,7 +998,8 @@ def main():
         # the timed data: this rank's chunks of ONE seeded global model (the N = 1 line's), so that
         # rank 0 checks the gathered model bit-for-bit against the oracle
         progress(f"chose {tname} R={R}; generating this rank's chunks of the global model")
-        ups_local, host_sample = global_chunks(cyc, K, P_total, a.dtype, device, a.seed, S if rank == 0 else 0)
+        ups_local, host_sample = global_chunks(cyc, K, P_total, a.dtype, device, a.seed,
+                                               S if a.full and rank == 0 else 0)
         agg = agg_all[:L]
         res = [None]
         step = make_step(cyc, tp, ups_local, res)
@@ -979,15 +1015,19 @@ def main():
             step()
         elapsed, _ = timed_steps(step, a.steps, stream, world, device, rehearsal)
         full = res[0]
-        # every rank ends the step holding the same model: int64 sum of its bits, compared over ranks
-        lo_bits, hi_bits = gathered_bits(full, device, rehearsal)
-        consistent = lo_bits == hi_bits
-        if tp is not None:
-            # every release grid after the peer stores covered every XCD (warm-up + timed steps)
-            extra["release_check"] = side(tp.check_release)
-        for _ in range(2):
-            fold_only()
-        _, kern_ms = timed_steps(fold_only, a.steps, stream, world, device, rehearsal)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"aggregate": full})
+        kern_ms = None
+        if a.full:
+            # every rank ends the step holding the same model: int64 sum of its bits, compared over ranks
+            lo_bits, hi_bits = gathered_bits(full, device, rehearsal)
+            extra["allgather_consistent_over_ranks"] = lo_bits == hi_bits
+            if tp is not None:
+                # every release grid after the peer stores covered every XCD (warm-up + timed steps)
+                extra["release_check"] = side(tp.check_release)
+            for _ in range(2):
+                fold_only()
+            _, kern_ms = timed_steps(fold_only, a.steps, stream, world, device, rehearsal)
         alg_bytes = K * L * in_bytes + L * 4              # this rank's fold, per step (all rounds)
         workload = f"fedavg_k{K}_p{L}_r{cyc.rounds}_{a.dtype}_rank_of_{world}"
         kernel = (f"{fold_kernel_label(cyc.C, in_bytes, K)} over this rank's {cyc.rounds} chunks of {cyc.C} params "
@@ -1009,8 +1049,7 @@ def main():
                   "transport": transport, "tuned_ms": tuned or None}
         scaling = "strong"
         extra["fold_allgather_ms"] = elapsed / a.steps * 1e3
-        extra["allgather_consistent_over_ranks"] = consistent
-        if rank == 0 and S:
+        if a.full and rank == 0 and S:
             progress("oracle check of the gathered model's sample")
             exact, dt = sample_check(full, host_sample, ns)
             base = {"value": K * S / dt, "unit": "params/s", "cores": 1, "kind": "port",
@@ -1019,7 +1058,7 @@ def main():
                               "cores present", "seconds": dt,
                     "gpu_bit_exact_on_sample": exact,
                     "gpu_sample_source": "rank 0's copy of the all-gathered model"}
-        if not a.no_side:
+        if a.full and not a.no_side:
             extra.update(multi_gpu_side(a, world, rank, device, rehearsal, ns, Ns, K, P_total, agg, ups_local, stream,
                                         rccl1, cyc, host_sample))
         if tp is not None:
@@ -1029,9 +1068,14 @@ def main():
                                     "collectives); not a reported number")
         ups = ups_local
 
-    achieved = alg_bytes / (kern_ms / 1e3) / 1e9
-    traffic, tsrc = pmc_traffic(workload)
-    if world == 1 and not rccl1:
+    roofline = None           # N > 1 without --full: the fold-only timing is a run of its own
+    if kern_ms is not None:
+        achieved = alg_bytes / (kern_ms / 1e3) / 1e9
+        traffic, tsrc = pmc_traffic(workload)
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                    "kernel": kernel, "kernel_ms": kern_ms, "alg_bytes_per_launch": alg_bytes}
+    if a.full and world == 1 and not rccl1:
         # the model to the host, FEDn's consumer (roundhandler.py:465-468); value excludes it
         host = torch.empty(P, dtype=torch.float32, pin_memory=True)
         for _ in range(2):
@@ -1066,13 +1110,11 @@ def main():
     if rank == 0:
         line = {
             "metric": METRIC, "value": K * P_total / (elapsed / a.steps), "unit": "params/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full, "ms_per_step": elapsed / a.steps * 1e3,
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": a.dtype,
             "data": "synthetic: base~N(0,1), client=base+0.01*N(0,1), num_examples~U{1..5000}, device-resident",
             "config": config,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                         "kernel": kernel, "kernel_ms": kern_ms, "alg_bytes_per_launch": alg_bytes},
+            "roofline": roofline,
             "cpu_baseline": base,
             # the north star's "absolute GB/s and fraction of the HBM roofline" for the whole job: the
             # algorithmic bytes of the 64-client fold over the GLOBAL model (K*P*s_in + P*4) per wall

@@ -3,6 +3,7 @@
 # Every GPU step has its own time limit; a crash / abort / timeout stops the session.
 # Usage: bash tools/gpu_session.sh [tag] [steps...]   (steps: test smoke bench prof)
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)   # the repository root, for the steps that run from another directory
 TAG=${1:-r01}; shift || true
 STEPS=${*:-test smoke bench prof}
 OUT=gpurun_out/$TAG
@@ -19,34 +20,34 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?
       echo "smoke rc=$rc"; tail -3 "$OUT/smoke.log"; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > "$OUT/bench.log" 2>&1; rc=$?
+      timeout -k 10 600 python bench.py --full > "$OUT/bench.log" 2>&1; rc=$?
       echo "bench rc=$rc"; tail -3 "$OUT/bench.log"; [ $rc -eq 0 ] || exit $rc ;;
     rehearsal)
       # the N>1 code path (strong-scaling line + side fields) with 2 ranks on this box's one GPU (gloo)
       FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --params 20000000 \
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --full --steps 5 --warmup 2 --params 20000000 \
         --clients 16 --fedopt-params 20000000 --waves-params 50000000 --waves-clients 32 > "$OUT/rehearsal.log" 2>&1; rc=$?
       echo "rehearsal rc=$rc"; grep -v amdgpu.ids "$OUT/rehearsal.log" | tail -3; [ $rc -eq 0 ] || exit $rc ;;
     selflaunch)
       # bench.py --gpus 2 WITHOUT torchrun (its own rank launcher), both ranks on this box's GPU (gloo)
-      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 --params 20000000 \
+      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 2 --full --steps 5 --warmup 2 --params 20000000 \
         --clients 16 --fedopt-params 20000000 --waves-params 50000000 --waves-clients 32 --cpu-sample 2000000 \
         --host-clients 4 > "$OUT/selflaunch.log" 2>&1; rc=$?
       echo "selflaunch rc=$rc"; grep -v amdgpu.ids "$OUT/selflaunch.log" | tail -3; [ $rc -eq 0 ] || exit $rc ;;
     selflaunch4)
       # the same with 4 ranks on this box's GPU (the N = 4 geometry: 4-way shards, 3 peers per rank)
-      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 4 --steps 5 --warmup 2 --params 20000000 \
+      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 600 python bench.py --gpus 4 --full --steps 5 --warmup 2 --params 20000000 \
         --clients 16 --fedopt-params 20000000 --waves-params 50000000 --waves-clients 32 --cpu-sample 2000000 \
         --host-clients 4 > "$OUT/selflaunch4.log" 2>&1; rc=$?
       echo "selflaunch4 rc=$rc"; grep -v amdgpu.ids "$OUT/selflaunch4.log" | tail -2 | cut -c1-400; [ $rc -eq 0 ] || exit $rc ;;
     selflaunch8)
       # bench.py --gpus 8 at DEFAULT sizes, self-launched, all 8 ranks on this box's one GPU
-      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 900 python bench.py --gpus 8 > "$OUT/selflaunch8.log" 2>&1; rc=$?
+      FEDN_AMD_BENCH_ONE_GPU=1 timeout -k 10 900 python bench.py --gpus 8 --full > "$OUT/selflaunch8.log" 2>&1; rc=$?
       echo "selflaunch8 rc=$rc"; grep -v amdgpu.ids "$OUT/selflaunch8.log" | tail -2 | cut -c1-600; [ $rc -eq 0 ] || exit $rc ;;
     rccl1)
       # the N>1 path at world size 1 over a real RCCL communicator (all-gathers as collectives, P2P fences)
       FEDN_AMD_BENCH_RCCL_WORLD1=1 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --steps 5 --warmup 2 --params 100000000 \
+        --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 1 --full --steps 5 --warmup 2 --params 100000000 \
         --clients 64 --fedopt-params 50000000 --waves-params 50000000 --waves-clients 32 --cpu-sample 2000000 \
         > "$OUT/rccl1.log" 2>&1; rc=$?
       echo "rccl1 rc=$rc"; grep -v amdgpu.ids "$OUT/rccl1.log" | tail -3; [ $rc -eq 0 ] || exit $rc ;;
@@ -168,7 +169,7 @@ for s in $STEPS; do
         i=$((i+1))
         for c in FETCH_SIZE WRITE_SIZE; do
           cd /tmp && timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/pmc$i/pmc_$c" -o run -- \
-            python3 "$GRAFT_REPO_ROOT/bench.py" --steps 3 --warmup 1 --cpu-sample 0 $args --no-side > "$GRAFT_REPO_ROOT/$OUT/pmc${i}_$c.log" 2>&1; rc=$?
+            python3 "$REPO/bench.py" --full --steps 3 --warmup 1 --cpu-sample 0 $args --no-side > "$REPO/$OUT/pmc${i}_$c.log" 2>&1; rc=$?
           cd "$GRAFT_REPO_ROOT"; echo "pmc$i $c rc=$rc"; [ $rc -eq 0 ] || exit $rc
         done
       done
@@ -215,7 +216,7 @@ for s in $STEPS; do
       python tools/pmc_probe_report.py "$OUT/pmcprobe" ;;
     prof)
       cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run -- \
-        python3 "$GRAFT_REPO_ROOT/bench.py" --steps 10 --warmup 2 --cpu-sample 0 --host-clients 0 > "$GRAFT_REPO_ROOT/$OUT/prof.log" 2>&1; rc=$?
+        python3 "$REPO/bench.py" --full --steps 10 --warmup 2 --cpu-sample 0 --host-clients 0 > "$REPO/$OUT/prof.log" 2>&1; rc=$?
       cd "$GRAFT_REPO_ROOT"; echo "prof rc=$rc"; tail -2 "$OUT/prof.log"; [ $rc -eq 0 ] || exit $rc ;;
   esac
 done
