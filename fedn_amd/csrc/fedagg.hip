@@ -2140,6 +2140,7 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
                   BLK == kBlock && MAP == 0 && !LT && !NT && NTS == 1) {
         if (g_cfg.avg_win_period > 0 && !int_first && !first) {
             const uint32_t wl = (uint32_t)g_cfg.avg_win_period.load(), ww = (uint32_t)g_cfg.avg_win_w.load();
+            g_kernel = "k_fedavg_pipe_win";
             hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), shm, st, a, tab,
                                cnt, P, wl, ww, g_cfg.avg_win_mode.load());
             return;

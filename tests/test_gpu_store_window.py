@@ -35,45 +35,56 @@ def test_fedavg_window_is_bit_identical(dev, K):
     out = {}
     with _abi.use_probe():
         try:
+            # this model is under the 160 MiB per client from which the product pipelines: AUTO_GEOM 0
+            # keeps the launch on launch_fedavg_pipe, where the window is chosen
+            ops.tune(auto_geom=0)
             for mode in (-1, 0, 7000):
                 ops.tune(avg_win_period=mode, avg_win_w=700)
                 agg = torch.empty(P, device=dev)
                 ops.fedavg_fold(agg, ups, ns, Ns, True)
+                assert ops.last_kernel() == ("k_fedavg_pipe" if mode < 0 else "k_fedavg_pipe_win"), mode
                 torch.cuda.synchronize()
                 out[mode] = agg
         finally:
-            ops.tune(avg_win_period=0)
+            ops.tune(auto_geom=1, avg_win_period=0, avg_win_w=0, avg_win_mode=0)
     assert _same(out[-1], out[0]) and _same(out[-1], out[7000])
 
 
-@pytest.mark.parametrize("phase", ["round1", "steady"])
+@pytest.mark.parametrize("phase", ["round1", "steady", "f32state"])
 def test_fedopt_window_is_bit_identical(dev, phase):
+    """round1: no state read; steady: fp64 m and v read; f32state: the fp32-state mode's round 1 and
+    steady state (out, v and m float32). Mode -1 must run k_fedopt_c and mode 0 k_fedopt_cw at every launch."""
     K = 32
     g = torch.Generator(device=dev).manual_seed(7)
     old32 = torch.randn(P, generator=g, device=dev)
     ups = [torch.randn(P, generator=g, device=dev).mul_(0.01).add_(old32) for _ in range(K)]
     ns = [int(v) for v in np.random.default_rng(3).integers(1, 5001, K)]
     Ns = [int(v) for v in np.cumsum(ns)]
+    sdt = torch.float32 if phase == "f32state" else torch.float64
     res = {}
     with _abi.use_probe():
         try:
             for mode in (-1, 0):
+                want = "k_fedopt_c" if mode < 0 else "k_fedopt_cw"
                 ops.tune(opt_win_period=mode, opt_win_prod=0)
-                out = torch.empty(P, dtype=torch.float64, device=dev)
-                v = torch.empty(P, dtype=torch.float64, device=dev)
+                out = torch.empty(P, dtype=sdt, device=dev)
+                v = torch.empty(P, dtype=sdt, device=dev)
                 m = torch.empty(P, dtype=torch.float32, device=dev)
                 ops.fedopt_step(old32, ups, ns, Ns, first=True, final=True, m_out=m, v_out=v, out=out)
-                if phase == "steady":
-                    old64, m64, v64 = out.clone(), m.double(), v.clone()
-                    m = torch.empty(P, dtype=torch.float64, device=dev)
-                    v = torch.empty(P, dtype=torch.float64, device=dev)
-                    out = torch.empty(P, dtype=torch.float64, device=dev)
-                    ops.fedopt_step(old64, ups, ns, Ns, first=True, final=True, m_in=m64, m_out=m, v_in=v64, v_out=v,
+                assert ops.last_kernel() == want, (mode, "round 1")
+                first = (out, m, v)
+                if phase != "round1":
+                    old2, m2, v2 = out.clone(), m.to(sdt), v.clone()
+                    m = torch.empty(P, dtype=sdt, device=dev)
+                    v = torch.empty(P, dtype=sdt, device=dev)
+                    out = torch.empty(P, dtype=sdt, device=dev)
+                    ops.fedopt_step(old2, ups, ns, Ns, first=True, final=True, m_in=m2, m_out=m, v_in=v2, v_out=v,
                                     out=out)
+                    assert ops.last_kernel() == want, (mode, "steady")
                 torch.cuda.synchronize()
-                res[mode] = (out, m, v)
+                res[mode] = first + (out, m, v)
         finally:
-            ops.tune(opt_win_period=0)
+            ops.tune(opt_win_period=0, opt_win_w=0, opt_win_prod=0)
     assert all(_same(a, b) for a, b in zip(res[-1], res[0]))
 
 
