@@ -25,12 +25,11 @@ FA_ADAM, FA_YOGI, FA_ADAGRAD = 0, 1, 2
 FA_PG_FIRST, FA_PG_FINAL = 1, 2
 (FA_EW_AXPBY, FA_EW_MUL, FA_EW_DIV, FA_EW_SQRT, FA_EW_SQUARE, FA_EW_SIGN, FA_EW_FILL, FA_EW_POW, FA_EW_IPOW, FA_EW_IFOLD,
  FA_EW_NFOLD) = range(11)
+# probe-library knobs (enum fa_tune_knob, include/fedagg_probe.h; tests/test_abi.py holds the two together)
 (FA_TUNE_STRIPS, FA_TUNE_UNROLL, FA_TUNE_NT, FA_TUNE_FASTDIV, FA_TUNE_LANETAB, FA_TUNE_GRID, FA_TUNE_READ,
- FA_TUNE_BLOCK, FA_TUNE_SUM_NOSTORE, FA_TUNE_NT_STORE, FA_TUNE_FASTDIV64, FA_TUNE_TILEMAP, FA_TUNE_OPT_NT,
- FA_TUNE_OPT_NOSTORE, FA_TUNE_OPT_STORE, FA_TUNE_OPT_COAL, FA_TUNE_NARROW, FA_TUNE_LDS, FA_TUNE_WPE, FA_TUNE_OPT_MV, FA_TUNE_AUTO_GEOM,
- FA_TUNE_OPT_MIX, FA_TUNE_OPT_BURST, FA_TUNE_OPT_G, FA_TUNE_OPT_WIN_PERIOD, FA_TUNE_OPT_WIN_W, FA_TUNE_OPT_WIN_MODE,
- FA_TUNE_AVG_WIN_PERIOD, FA_TUNE_AVG_WIN_W, FA_TUNE_AVG_WIN_MODE, FA_TUNE_OPT_WIN_PROD,
- FA_TUNE_OPT_QUAD) = range(32)
+ FA_TUNE_BLOCK, FA_TUNE_SUM_NOSTORE, FA_TUNE_NT_STORE, FA_TUNE_FASTDIV64, FA_TUNE_NARROW, FA_TUNE_AUTO_GEOM,
+ FA_TUNE_OPT_MIX, FA_TUNE_OPT_WIN_PERIOD, FA_TUNE_OPT_WIN_W, FA_TUNE_OPT_WIN_MODE,
+ FA_TUNE_AVG_WIN_PERIOD, FA_TUNE_AVG_WIN_W, FA_TUNE_AVG_WIN_MODE, FA_TUNE_OPT_WIN_PROD) = range(21)
 
 EXPORTS = {
     # name: (restype, argtypes)

@@ -662,12 +662,12 @@ struct LaneTable {
 }
 
 
-// Workgroup -> tile order for the one-tile-per-workgroup grid (fa_tune FA_TUNE_TILEMAP).
+// Workgroup -> tile order for the one-tile-per-workgroup grid. Only MAP 0 is instantiated.
 // Workgroups are dealt round-robin to the 8 XCDs, so with MAP 0 consecutive tiles run on
 // different XCDs. MAP = R > 0 gives each XCD runs of R consecutive tiles (groups of 8R tiles,
 // XCD x taking tiles [xR, xR + R) of each group): a bijection on the first whole groups and
-// the identity on the rest. (One contiguous eighth of the model per XCD measured 0.5-4 %
-// slower than identity: profiles/r01_tilemap.log.)
+// the identity on the rest. (Runs of 2...32 measured within 1 % of identity, one contiguous
+// eighth of the model per XCD 0.5-4 % slower: DESIGN.md §4.)
 template <int MAP>
 __device__ __forceinline__ int64_t map_tile(int64_t t, int64_t ntiles) {
     if constexpr (MAP > 0) {
@@ -765,16 +765,6 @@ k_fedavg_pipe_win(X* __restrict__ agg, const ClientTable<typename CP::S> tab, co
                   const uint32_t period, const uint32_t win_w, const int win_mode) {
     fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP, true>(agg, tab, K, P, period, win_w, win_mode);
 }
-
-#ifdef FEDAGG_PROBES
-// occupancy probe (FA_TUNE_WPE): the same body compiled for at least W waves per SIMD
-template <typename Y, typename X, class CP, int E, int S, bool INIT, bool INT_FIRST, bool NT, bool LT, int BLK, int NTS,
-          int MAP, int W>
-__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(W)))
-k_fedavg_pipe_w(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const int K, const int64_t P) {
-    fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP>(agg, tab, K, P);
-}
-#endif
 
 // ----------------------------------------------------------------------------
 // FedOpt kernel: pseudo-gradient fold + server step, fused
@@ -1079,8 +1069,8 @@ __device__ __forceinline__ void fedopt_strip(const OptBuffers& b, const OptScala
 // owns the pairs {2L, 2L+1} + 128 j, j < NH, so every 8-byte stream (old, m, v, pg, out) moves one
 // contiguous 1 KiB per wave instruction (full 128-B lines, no half-line stores) and the client loads
 // are contiguous 512-B dwordx2 wave instructions. Whole wave tiles only.
-// H (probe builds only, FA_TUNE_OPT_QUAD): elements per lane per strip — 2 (the product: pairs) or 4
-// (quads at lane stride 4: 2-byte client loads become dwordx2, 8-byte streams two dwordx4 per strip).
+// H: elements per lane per strip — 2 (pairs; the only value instantiated) or 4 (quads at lane
+// stride 4: 2-byte client loads become dwordx2, 8-byte streams two dwordx4 per strip; a null result).
 template <typename Y, typename OLD, class PG, bool FIRST, bool FINAL, bool NT, int OSM = 0, int NH = 2,
           int U = kUnroll / 2, bool WIN = false, int H = 2>
 __device__ __forceinline__ void fedopt_strip_split(const OptBuffers& b, const OptScalars& s,
@@ -1172,7 +1162,7 @@ __device__ __forceinline__ void fedopt_c_body(const OptBuffers& b, const OptScal
     const int64_t base = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * T;
     const int lane = threadIdx.x & 63;
     if constexpr (MV) {
-        // layout probe (FA_TUNE_OPT_MV): fp64 m and v interleaved per wave tile in one buffer
+        // layout probe (never instantiated now): fp64 m and v interleaved per wave tile in one buffer
         // ([m of tile w | v of tile w] at 2wT), read from m_in and written to m_out; whole tiles only
         if (base + T > P) return;
         OptBuffers bb = b;
@@ -1193,207 +1183,6 @@ __device__ __forceinline__ void fedopt_c_body(const OptBuffers& b, const OptScal
         }
     }
 }
-
-#ifdef FEDAGG_PROBES
-// burst-store probe of the product step (FA_TUNE_OPT_G = G): k_fedopt_c's FINAL phase
-// with every wave taking G consecutive 512-element tiles and storing the new v / out / m of all G
-// after the last tile's reads (k_fedopt_mixg measured the access pattern alone). The arithmetic is
-// opt_apply's, duplicated here (opt_compute_p) so that the product kernels' code stays as measured.
-template <class PG, int E>
-__device__ __forceinline__ void opt_compute_p(const OptBuffers& b, const OptScalars& s, const typename PG::V (&pg)[E],
-                                              const typename PG::V (&ov)[E], const double (&mi)[E], double (&v)[E],
-                                              double (&m)[E], double (&o)[E]) {
-    using V = typename PG::V;
-    constexpr bool PG32 = std::is_same<PG, CF32>::value;
-    // ---- m (fedopt.py:173-176 and the two twins)
-    constexpr bool PG64 = std::is_same<PG, CF64>::value;
-    if (b.m_in_f64 < 0) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) m[e] = mul_pg<PG>((double)pg[e], s.c1, s.c1f, s.c1h);
-    } else {
-        // m*beta1 in m's dtype, pg*(1-beta1) in pg's dtype, their sum in the promoted dtype
-        // (f16 < f32 < f64); each operand is exact in its dtype, so the float sum rounds once
-        if (b.m_in_f64 == 1) {                     // f64 m: an f64 sum
-#pragma unroll
-            for (int e = 0; e < E; ++e) m[e] = mi[e] * s.b1 + mul_pg<PG>((double)pg[e], s.c1, s.c1f, s.c1h);
-        } else if (b.m_in_f64 == 0) {              // f32 m (mi is an exact f32)
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const float a = (float)mi[e] * s.b1f;
-                const double pm = mul_pg<PG>((double)pg[e], s.c1, s.c1f, s.c1h);
-                if constexpr (PG64) m[e] = (double)a + pm;          // f32 + f64
-                else m[e] = (double)(a + (float)pm);                // f32 + f32 (or f16) in f32
-            }
-        } else {                                   // f16 m (a float16 session's first rounds)
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const float a = CF16::rh((float)mi[e] * s.b1h);
-                const double pm = mul_pg<PG>((double)pg[e], s.c1, s.c1f, s.c1h);
-                if constexpr (PG64) m[e] = (double)a + pm;
-                else if constexpr (PG32) m[e] = (double)(a + (float)pm);
-                else m[e] = (double)CF16::rh(a + (float)pm);
-            }
-        }
-    }
-    // ---- v (fedopt.py:178-179 / 214-217 / 251-252)
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const V pv = pg[e];
-        const double p = (double)pg_sq<PG>(pv);   // power(pg, 2) in the pg dtype
-        if (s.opt == FA_ADAM) {
-            v[e] = v[e] * s.b2 + mul_pg<PG>(p, s.c2, s.c2f, s.c2h);
-        } else if (s.opt == FA_YOGI) {
-            const double sg = np_sign(v[e] - p);
-            v[e] = v[e] + (sg * p) * s.nc2;
-        } else {
-            v[e] = v[e] + p;
-        }
-        const double sv = __builtin_sqrt(v[e]) + s.tau;
-        const double t = m[e] / sv;
-        o[e] = (double)ov[e] + t * s.lr;
-    }
-}
-
-template <typename Y, typename OLD, class PG, bool FIRST, bool NT, int G, bool WIN = false>
-__device__ __forceinline__ void fedopt_cg_body(const OptBuffers& b, const OptScalars& s, const ClientTable<typename PG::S>& tab,
-                                               const int K, const int64_t P, const uint32_t period = 0,
-                                               const uint32_t win_w = 0) {
-    using V = typename PG::V;
-    constexpr int NH = 4, H = 2, E = H * NH, U = kUnroll / 2;
-    constexpr int64_t T = 128 * NH;
-    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if ((wave + 1) * G * T > P) {                 // a partial group: the product kernel's per-tile path
-        for (int g = 0; g < G; ++g) {
-            const int64_t base = (wave * G + g) * T;
-            if (base >= P) break;
-            if (base + T <= P) fedopt_strip_split<Y, OLD, PG, FIRST, true, NT, 1, NH, U>(b, s, tab, K, base + 2 * lane);
-            else
-                for (int j = 0; j < NH / 2; ++j) {
-                    const int64_t i0 = base + j * 256 + 4 * lane;
-                    if (i0 < P) fedopt_strip<Y, OLD, PG, 4, FIRST, true, NT, false, 1>(b, s, tab, K, P, i0);
-                }
-        }
-        return;
-    }
-    double mo[G][E], vo[G][E], oo[G][E];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int64_t i0 = (wave * G + g) * T + 2 * lane;
-        auto half = [](auto& a, int h) -> auto& {
-            using TT = std::remove_reference_t<decltype(a[0])>;
-            return *reinterpret_cast<TT(*)[H]>(&a[h * H]);
-        };
-        auto at = [i0](int h) { return i0 + (int64_t)h * 128; };
-        OLD old[E];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) strip_load<OLD, H, false>(static_cast<const OLD*>(b.old) + at(h), half(old, h));
-        V ov[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) ov[e] = widen<OLD, V>(old[e]);
-        V pg[E];
-        int k = 0;
-        if constexpr (FIRST) {
-            Y y[E];
-            const Y* yp = static_cast<const Y*>(tab.ptr[0]);
-#pragma unroll
-            for (int h = 0; h < NH; ++h) strip_load<Y, H, NT>(yp + at(h), half(y, h));
-#pragma unroll
-            for (int e = 0; e < E; ++e) pg[e] = pg_sub<PG>(widen<Y, V>(y[e]), ov[e]);
-            k = 1;
-        } else {
-            using TT = typename PG::T;
-            TT t[E];
-#pragma unroll
-            for (int h = 0; h < NH; ++h) strip_load<TT, H, false>(static_cast<const TT*>(b.pg) + at(h), half(t, h));
-#pragma unroll
-            for (int e = 0; e < E; ++e) pg[e] = widen<TT, V>(t[e]);
-        }
-        for (; k + U <= K; k += U) {
-            Y y[U][E];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const Y* yp = static_cast<const Y*>(tab.ptr[k + u]);
-#pragma unroll
-                for (int h = 0; h < NH; ++h) strip_load<Y, H, NT>(yp + at(h), half(y[u], h));
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                V d[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) d[e] = pg_sub<PG>(widen<Y, V>(y[u][e]), ov[e]);
-                fold_strip<PG, E>(pg, d, tab.n[k + u], tab.N[k + u], tab.r[k + u]);
-            }
-        }
-        for (; k < K; ++k) {
-            const Y* yp = static_cast<const Y*>(tab.ptr[k]);
-            Y y[E];
-#pragma unroll
-            for (int h = 0; h < NH; ++h) strip_load<Y, H, NT>(yp + at(h), half(y, h));
-            V d[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) d[e] = pg_sub<PG>(widen<Y, V>(y[e]), ov[e]);
-            fold_strip<PG, E>(pg, d, tab.n[k], tab.N[k], tab.r[k]);
-        }
-        double mi[E];
-#pragma unroll
-        for (int h = 0; h < NH; ++h) opt_load_state<H>(b, s, at(h), H, half(mi, h), half(vo[g], h));
-#pragma unroll
-        for (int h = 0; h < NH; ++h)
-            opt_compute_p<PG, H>(b, s, half(pg, h), half(ov, h), half(mi, h), half(vo[g], h), half(mo[g], h), half(oo[g], h));
-    }
-    if constexpr (WIN) wait_write_window(period, win_w);      // everything computed: only the stores wait
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int64_t i0 = (wave * G + g) * T + 2 * lane;
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const int64_t o = i0 + (int64_t)h * 128;
-            double* vp = &vo[g][h * H];
-            double* op = &oo[g][h * H];
-            double* mp = &mo[g][h * H];
-            // fp64 state and model (the steady state of configs[3]; other dtypes refused at launch)
-            strip_store<double, H, 1>(static_cast<double*>(b.v_out) + o, *reinterpret_cast<double(*)[H]>(vp));
-            strip_store<double, H, 1>(static_cast<double*>(b.out) + o, *reinterpret_cast<double(*)[H]>(op));
-            strip_store<double, H, 1>(static_cast<double*>(b.m_out) + o, *reinterpret_cast<double(*)[H]>(mp));
-        }
-    }
-}
-
-template <typename Y, typename OLD, class PG, bool FIRST, bool NT, int G>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_cg(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P) {
-    fedopt_cg_body<Y, OLD, PG, FIRST, NT, G>(b, s, tab, K, P);
-}
-
-// the windowed product step compiled for at least W waves per SIMD (FA_TUNE_WPE with a window): the
-// waves idling for their window need other waves resident to keep the reads flowing
-template <typename Y, typename OLD, class PG, bool NT, int W>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W)))
-k_fedopt_cw_w(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P,
-              const uint32_t period, const uint32_t win_w) {
-    fedopt_c_body<Y, OLD, PG, true, true, NT, 1, 4, kUnroll / 2, false, true>(b, s, tab, K, P, period, win_w);
-}
-
-// the windowed step on 256-element wave tiles (2 pairs per lane; OPT_WIN_PROD = 3): fewer registers
-// held per wave, so more waves resident to keep reading while others wait for their window
-template <typename Y, typename OLD, class PG, bool NT>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_cw2(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P,
-             const uint32_t period, const uint32_t win_w) {
-    fedopt_c_body<Y, OLD, PG, true, true, NT, 1, 2, kUnroll / 2, false, true>(b, s, tab, K, P, period, win_w);
-}
-
-// store-window probe on the compute-then-store order (OPT_WIN_PROD = 2): one tile per wave, its
-// v / out / m computed first and stored inside the window (k_fedopt_cw waits before opt_apply, so
-// its fp64 square roots and divisions run inside the window)
-template <typename Y, typename OLD, class PG, bool NT>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_cgw(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P,
-             const uint32_t period, const uint32_t win_w) {
-    fedopt_cg_body<Y, OLD, PG, true, NT, 1, true>(b, s, tab, K, P, period, win_w);
-}
-#endif
 
 template <typename Y, typename OLD, class PG, bool FIRST, bool FINAL, bool NT, int OSM = 0, int NH = 2,
           int U = kUnroll / 2>
@@ -1426,40 +1215,6 @@ __global__ void __launch_bounds__(kBlock)
 k_fedopt_cwp(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P,
              const uint32_t period, const uint32_t win_w) {
     fedopt_c_body<Y, OLD, PG, FIRST, false, NT, 1, 4, kUnroll / 2, false, true>(b, s, tab, K, P, period, win_w);
-}
-#endif
-
-#ifdef FEDAGG_PROBES
-// element-map probe (FA_TUNE_OPT_QUAD): k_fedopt_c's 512-element wave tiles with lane L owning the
-// quads {4L .. 4L+3} + 256 j, j < 2, instead of the pairs {2L, 2L+1} + 128 j, j < 4. Same elements
-// per lane, same arithmetic per element: bit-identical. 2-byte client loads widen from one dword to
-// one dwordx2 per strip; the 8-byte streams (old, pg, m, v, out) take two dwordx4 per strip.
-template <typename Y, typename OLD, class PG, bool FIRST, bool FINAL, bool NT>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_cq(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P) {
-    const int64_t base = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 512;
-    const int lane = threadIdx.x & 63;
-    if (base + 512 <= P) {
-        fedopt_strip_split<Y, OLD, PG, FIRST, FINAL, NT, 1, 2, kUnroll / 2, false, 4>(b, s, tab, K, base + 4 * lane);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int64_t i0 = base + j * 256 + 4 * lane;
-            if (i0 < P) fedopt_strip<Y, OLD, PG, 4, FIRST, FINAL, NT, false, 1>(b, s, tab, K, P, i0);
-        }
-    }
-}
-
-template <typename Y, typename OLD, class PG, bool FIRST, bool FINAL, bool NT, int OSM, int NH, int U, int W>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W)))
-k_fedopt_c_w(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P) {
-    fedopt_c_body<Y, OLD, PG, FIRST, FINAL, NT, OSM, NH, U>(b, s, tab, K, P);
-}
-
-template <typename Y, typename OLD, class PG, bool NT>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_c_mv(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::S> tab, const int K, const int64_t P) {
-    fedopt_c_body<Y, OLD, PG, true, true, NT, 1, 4, kUnroll / 2, true>(b, s, tab, K, P);
 }
 
 // access-pattern probe (FA_TUNE_OPT_MIX): exactly k_fedopt_c's loads and stores for a FIRST|FINAL
@@ -1533,83 +1288,7 @@ k_fedopt_mix(const OptBuffers b, const ClientTable<S> tab, const int K, const in
         }
     }
 }
-#endif
 
-#ifdef FEDAGG_PROBES
-// burst-store probe (FA_TUNE_OPT_BURST = G): k_fedopt_mix's access pattern, but each
-// wave takes G consecutive wave tiles and holds the new v / out / m of all G in registers (LDS
-// staging of several tiles would leave one workgroup per CU), storing them together after the
-// reads of the last one — the writes leave the wave in one burst of 3 x G KiB-lines per stream
-// instead of interleaved with every tile's reads. Whole groups of G tiles only.
-template <typename Y, typename OLD, typename S, bool NT, int G>
-__global__ void __launch_bounds__(kBlock)
-k_fedopt_mixg(const OptBuffers b, const ClientTable<S> tab, const int K, const int64_t P) {
-    constexpr int NH = 4, H = 2, E = 2 * NH, U = kUnroll / 2;
-    constexpr int64_t T = 128 * NH;
-    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-    if ((wave + 1) * G * T > P) return;
-    double vo[G][E], oo[G][E], mo[G][E];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int64_t i0 = (wave * G + g) * T + 2 * (threadIdx.x & 63);
-        auto at = [i0](int h) { return i0 + (int64_t)h * 128; };
-        double acc[E];
-        {
-            OLD old[E];
-#pragma unroll
-            for (int h = 0; h < NH; ++h)
-                strip_load<OLD, H, false>(static_cast<const OLD*>(b.old) + at(h), *reinterpret_cast<OLD(*)[H]>(&old[h * H]));
-#pragma unroll
-            for (int e = 0; e < E; ++e) acc[e] = (double)widen<OLD, double>(old[e]);
-        }
-        auto add_client = [&](int k, Y (&y)[E]) {
-            const Y* yp = static_cast<const Y*>(tab.ptr[k]);
-#pragma unroll
-            for (int h = 0; h < NH; ++h) strip_load<Y, H, NT>(yp + at(h), *reinterpret_cast<Y(*)[H]>(&y[h * H]));
-        };
-        int k = 0;
-        for (; k + U <= K; k += U) {
-            Y y[U][E];
-#pragma unroll
-            for (int u = 0; u < U; ++u) add_client(k + u, y[u]);
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc[e] += (double)widen<Y, double>(y[u][e]);
-        }
-        for (; k < K; ++k) {
-            Y y[E];
-            add_client(k, y);
-#pragma unroll
-            for (int e = 0; e < E; ++e) acc[e] += (double)widen<Y, double>(y[e]);
-        }
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            double mi[H] = {}, vv[H] = {};
-            opt_load_state<H>(b, OptScalars{}, at(h), H, mi, vv);
-#pragma unroll
-            for (int e = 0; e < H; ++e) {
-                mo[g][h * H + e] = mi[e] + acc[h * H + e];
-                vo[g][h * H + e] = vv[e] + acc[h * H + e];
-                oo[g][h * H + e] = acc[h * H + e];
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const int64_t i0 = (wave * G + g) * T + 2 * (threadIdx.x & 63);
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const int64_t o = i0 + (int64_t)h * 128;
-            strip_store<double, H, 1>(static_cast<double*>(b.v_out) + o, *reinterpret_cast<double(*)[H]>(&vo[g][h * H]));
-            strip_store<double, H, 1>(static_cast<double*>(b.out) + o, *reinterpret_cast<double(*)[H]>(&oo[g][h * H]));
-            strip_store<double, H, 1>(static_cast<double*>(b.m_out) + o, *reinterpret_cast<double(*)[H]>(&mo[g][h * H]));
-        }
-    }
-}
-#endif
-
-#ifdef FEDAGG_PROBES
 // clock-windowed store probe (FA_TUNE_OPT_WIN_*): k_fedopt_mix's access pattern with the whole chip's
 // stores confined to a common time window. Every wave reads the GPU's 100 MHz reference clock
 // (s_memrealtime, one counter for all XCDs) and issues its v / out / m stores only while
@@ -1970,7 +1649,9 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 #ifdef FEDAGG_PROBES
 struct FedAvgCfg {
     std::atomic<int> strips{4}, unroll{0}, lanetab{0}, grid_per_cu{0}, read_per_lane{16}, block_log{8},
-        sum_nostore{0}, nt_store{1}, nt{0}, tilemap{0}, fastdiv{1}, fastdiv64{1}, opt_nt{1}, opt_nostore{0}, opt_store{0}, opt_coal{2}, narrow{1}, lds_kib{0}, wpe{0}, opt_mv{0}, auto_geom{1}, opt_mix{0}, opt_burst{0}, opt_g{0}, opt_win_period{0}, opt_win_w{0}, opt_win_mode{0}, avg_win_period{0}, avg_win_w{0}, avg_win_mode{0}, opt_win_prod{0}, opt_quad{0};
+        sum_nostore{0}, nt_store{1}, nt{0}, fastdiv{1}, fastdiv64{1}, narrow{1}, auto_geom{1}, opt_mix{0},
+        opt_win_period{0}, opt_win_w{0}, opt_win_mode{0}, opt_win_prod{0}, avg_win_period{0}, avg_win_w{0},
+        avg_win_mode{0};
 };
 FedAvgCfg g_cfg;
 int cfg_fastdiv() { return g_cfg.fastdiv.load(std::memory_order_relaxed); }
@@ -2099,7 +1780,160 @@ AvgWindow avg_store_window(int K, int64_t P) {
     return w;
 }
 
+// the launch functions (defined below) that the probe build's geometry sweep dispatches to
 template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK = kBlock, int NTS = 0, int MAP = 0>
+void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                        hipStream_t st);
+template <typename Y, typename X, class CP, int E, int S, int U, bool NT>
+void launch_fedavg_geom(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                        hipStream_t st);
+template <typename Y, typename X, class CP, int E>
+void launch_fedavg_small(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                         hipStream_t st);
+template <typename Y>
+inline bool pipe_pays(int64_t P);
+
+#ifdef FEDAGG_PROBES
+// ----------------------------------------------------------------------------
+// probe overrides (libfedagg_probe.so only): everything the fa_tune knobs change in the launch
+// functions below. Each hook leaves the product's choice alone while its knobs are at their defaults.
+// ----------------------------------------------------------------------------
+
+// AVG_WIN_PERIOD / _W / _MODE on a first fold launch: -1 = no window, > 0 = this one
+void probe_avg_window(AvgWindow& w, int& mode) {
+    const int period = g_cfg.avg_win_period;
+    if (period < 0) w = AvgWindow{};
+    else if (period > 0) {
+        w = AvgWindow{(uint32_t)period, (uint32_t)g_cfg.avg_win_w.load()};
+        mode = g_cfg.avg_win_mode.load();
+    }
+}
+
+// AVG_WIN_PERIOD > 0 on a continuation launch (K > 64) of the fp32 fold: windowed too, which the
+// product never does (k_fedavg_pipe_win's INIT = false instantiation)
+template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
+bool probe_avg_window_cont(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                           dim3 grid, hipStream_t st) {
+    if constexpr (std::is_same<CP, CF32>::value && std::is_same<X, float>::value && S * E * (int)sizeof(Y) == 64 &&
+                  BLK == kBlock && MAP == 0 && !LT && !NT && NTS == 1) {
+        if (g_cfg.avg_win_period > 0 && !int_first && !first) {
+            const uint32_t wl = (uint32_t)g_cfg.avg_win_period.load(), ww = (uint32_t)g_cfg.avg_win_w.load();
+            g_kernel = "k_fedavg_pipe_win";
+            hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a, tab,
+                               cnt, P, wl, ww, g_cfg.avg_win_mode.load());
+            return true;
+        }
+    }
+    return false;
+}
+
+// The FedAvg geometry sweep (STRIPS, UNROLL, NT, LANETAB, BLOCK, NT_STORE, NARROW, AUTO_GEOM) of the
+// fp32 / bf16 -> fp32 fold: false while every one of these knobs is at its default (the caller then
+// makes the product's choice, launch_fedavg_default); otherwise launches the instantiated geometry,
+// or 1 x 8 for a combination that is not instantiated. GRID is no part of this: launch_fedavg_pipe
+// applies it to whichever pipelined geometry is chosen, the product's included.
+template <typename Y, typename X, class CP, int E>
+bool probe_fedavg_geometry(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                           hipStream_t st) {
+    const int block_log = g_cfg.block_log, strips = g_cfg.strips, unroll = g_cfg.unroll, nt = g_cfg.nt;
+    const int lanetab = g_cfg.lanetab, nt_store = g_cfg.nt_store;
+    const int key = (block_log == 9 ? 20000 : block_log == 10 ? 30000 : 0) + lanetab * 10000 + strips * 100 +
+                    unroll * 2 + nt;
+    constexpr bool narrowable = sizeof(Y) < sizeof(X) && E % 2 == 0;
+    if (key == 4 * 100 + 0 && nt_store == 1) {
+        if (g_cfg.auto_geom && (g_cfg.narrow || !narrowable)) return false;   // every knob at its default
+        // NARROW 0 keeps the size rule; AUTO_GEOM 0 forces the pipelined kernel at every size
+        if (g_cfg.auto_geom && !pipe_pays<Y>(P)) {
+            launch_fedavg_small<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st);
+            return true;
+        }
+        if constexpr (narrowable) {
+            if (g_cfg.narrow) {
+                launch_fedavg_pipe<Y, X, CP, E / 2, 8, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
+                return true;
+            }
+        }
+    }
+    switch (key) {
+#define FA_GEOM(S_, U_, NT_) \
+    case S_ * 100 + U_ * 2 + NT_: launch_fedavg_geom<Y, X, CP, E, S_, U_, NT_>(a, tab, cnt, P, first, int_first, st); return true;
+#define FA_PIPE(KEY_, ...) \
+    case KEY_: launch_fedavg_pipe<Y, X, CP, E, __VA_ARGS__>(a, tab, cnt, P, first, int_first, st); return true;
+        FA_GEOM(1, 4, 0) FA_GEOM(1, 8, 0) FA_GEOM(1, 16, 0) FA_GEOM(2, 4, 0) FA_GEOM(2, 8, 0) FA_GEOM(2, 16, 0)
+        FA_GEOM(4, 1, 0) FA_GEOM(4, 2, 0) FA_GEOM(4, 4, 0) FA_GEOM(8, 1, 0) FA_GEOM(8, 2, 0) FA_GEOM(16, 1, 0)
+        FA_GEOM(1, 8, 1) FA_GEOM(4, 2, 1) FA_GEOM(8, 1, 1)
+        FA_PIPE(2 * 100 + 0, 2, false, false)
+        case 4 * 100 + 0:
+            if (nt_store == 1) launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
+            else if (nt_store == 2) launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 2>(a, tab, cnt, P, first, int_first, st);
+            else launch_fedavg_pipe<Y, X, CP, E, 4, false, false>(a, tab, cnt, P, first, int_first, st);
+            return true;
+        FA_PIPE(8 * 100 + 0, 8, false, false)
+        FA_PIPE(4 * 100 + 1, 4, true, false)
+        FA_PIPE(20000 + 4 * 100 + 0, 4, false, false, 512)
+        FA_PIPE(30000 + 4 * 100 + 0, 4, false, false, 1024)
+        FA_PIPE(20000 + 8 * 100 + 0, 8, false, false, 512)
+        FA_PIPE(30000 + 2 * 100 + 0, 2, false, false, 1024)
+        FA_PIPE(10000 + 2 * 100 + 0, 2, false, true)
+        FA_PIPE(10000 + 4 * 100 + 0, 4, false, true)
+        FA_PIPE(10000 + 8 * 100 + 0, 8, false, true)
+#undef FA_PIPE
+#undef FA_GEOM
+        default: break;
+    }
+    launch_fedavg_geom<Y, X, CP, E, 1, kUnroll, false>(a, tab, cnt, P, first, int_first, st);
+    return true;
+}
+
+// FedOpt launches of the vector path (E = 4) that replace the product step: the access-pattern
+// probes of a FIRST | FINAL launch (OPT_MIX, and OPT_WIN_PERIOD > 0 without OPT_WIN_PROD:
+// k_fedopt_mixw) — instantiated for the configs[3] shapes only, fp32 updates over an fp32 or fp64
+// model — and the store window on a first or middle launch of a multi-launch round (OPT_WIN_PERIOD
+// > 0 with OPT_WIN_PROD: k_fedopt_cwp, every dtype). True: launched, or refused, with the status in rc.
+template <typename Y, typename OLD, class PG, bool NT>
+bool probe_fedopt_launch(const OptBuffers& b, const OptScalars& s, const ClientTable<typename PG::S>& tab, int cnt, int64_t P,
+                         bool first, bool final_, dim3 g4, hipStream_t st, int& rc) {
+    constexpr bool probe_combo = std::is_same<Y, float>::value && (std::is_same<OLD, float>::value || std::is_same<OLD, double>::value);
+    const int period = g_cfg.opt_win_period, prod = g_cfg.opt_win_prod;
+    if constexpr (probe_combo) {                         // (g4: a ragged last tile is skipped)
+        if (first && final_ && period > 0 && !prod) {
+            if (b.m_out_f64 != 1) {
+                rc = fail(FA_EINVAL, "fa_tune OPT_WIN probe: fp64 m out");
+                return true;
+            }
+            hipLaunchKernelGGL((k_fedopt_mixw<Y, OLD, typename PG::S, NT>), g4, dim3(kBlock), 0, st, b, tab, cnt, P, (uint32_t)period,
+                               (uint32_t)g_cfg.opt_win_w.load(), g_cfg.opt_win_mode.load());
+            rc = check_launch("fa_fedopt_step: kernel launch");
+            return true;
+        }
+        if (first && final_ && g_cfg.opt_mix) {
+            hipLaunchKernelGGL((k_fedopt_mix<Y, OLD, typename PG::S, NT>), g4, dim3(kBlock), 0, st, b, tab, cnt, P);
+            rc = check_launch("fa_fedopt_step: kernel launch");
+            return true;
+        }
+    }
+    if (!final_ && period > 0 && prod) {
+        const uint32_t w = (uint32_t)g_cfg.opt_win_w.load();
+        if (first)
+            hipLaunchKernelGGL((k_fedopt_cwp<Y, OLD, PG, true, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, (uint32_t)period, w);
+        else
+            hipLaunchKernelGGL((k_fedopt_cwp<Y, OLD, PG, false, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, (uint32_t)period, w);
+        rc = check_launch("fa_fedopt_step: kernel launch");
+        return true;
+    }
+    return false;
+}
+
+// OPT_WIN_PERIOD on the product's single-launch step (k_fedopt_cw): -1 = no window, > 0 with
+// OPT_WIN_PROD = this one
+void probe_opt_window(StoreWindow& sw) {
+    const int period = g_cfg.opt_win_period;
+    if (period < 0) sw = StoreWindow{};
+    else if (period > 0 && g_cfg.opt_win_prod) sw = StoreWindow{(uint32_t)period, (uint32_t)g_cfg.opt_win_w.load()};
+}
+#endif  // FEDAGG_PROBES
+
+template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
 void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
                         hipStream_t st) {
     g_kernel = "k_fedavg_pipe";
@@ -2110,7 +1944,6 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
         ntiles = std::min<int64_t>(ntiles, (int64_t)cfg_grid_per_cu() * device_cus());
     }
     const dim3 grid((unsigned)ntiles);
-    unsigned shm = 0;
     // the fp32 fold with a first launch (the BASELINE workload's shape): its stores in the chip-wide
     // window; other dtypes / continuation launches were not measured with one
     if constexpr (std::is_same<CP, CF32>::value && std::is_same<X, float>::value &&
@@ -2120,11 +1953,7 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
             AvgWindow w = avg_store_window<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(cnt, P);
             int wm = 0;
 #ifdef FEDAGG_PROBES
-            if (g_cfg.avg_win_period < 0 || g_cfg.wpe > 0 || g_cfg.lds_kib > 0) w = AvgWindow{};   // A/B and the other probes
-            else if (g_cfg.avg_win_period > 0) {
-                w = AvgWindow{(uint32_t)g_cfg.avg_win_period.load(), (uint32_t)g_cfg.avg_win_w.load()};
-                wm = g_cfg.avg_win_mode.load();
-            }
+            probe_avg_window(w, wm);
 #endif
             if (w.period) {
                 g_kernel = "k_fedavg_pipe_win";
@@ -2135,36 +1964,15 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
         }
     }
 #ifdef FEDAGG_PROBES
-    shm = (unsigned)g_cfg.lds_kib * 1024u;     // occupancy probe: LDS the kernel never touches
-    if constexpr (std::is_same<CP, CF32>::value && std::is_same<X, float>::value && S * E * (int)sizeof(Y) == 64 &&
-                  BLK == kBlock && MAP == 0 && !LT && !NT && NTS == 1) {
-        if (g_cfg.avg_win_period > 0 && !int_first && !first) {
-            const uint32_t wl = (uint32_t)g_cfg.avg_win_period.load(), ww = (uint32_t)g_cfg.avg_win_w.load();
-            g_kernel = "k_fedavg_pipe_win";
-            hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), shm, st, a, tab,
-                               cnt, P, wl, ww, g_cfg.avg_win_mode.load());
-            return;
-        }
-        const int w = g_cfg.wpe;
-        if (w > 0 && !int_first) {
-#define FA_WPE(W_)                                                                                                      \
-    if (w == W_) {                                                                                                      \
-        if (first) hipLaunchKernelGGL((k_fedavg_pipe_w<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, W_>), grid, dim3(BLK), shm, st, a, tab, cnt, P); \
-        else hipLaunchKernelGGL((k_fedavg_pipe_w<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP, W_>), grid, dim3(BLK), shm, st, a, tab, cnt, P); \
-        return;                                                                                                         \
-    }
-            FA_WPE(5) FA_WPE(6) FA_WPE(8)
-#undef FA_WPE
-        }
-    }
+    if (probe_avg_window_cont<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(a, tab, cnt, P, first, int_first, grid, st)) return;
 #endif
     if (first && int_first) {
         if constexpr (std::is_integral<Y>::value)
-            hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, true, true, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), shm, st, a, tab, cnt, P);
+            hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, true, true, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a, tab, cnt, P);
     } else if (first)
-        hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), shm, st, a, tab, cnt, P);
+        hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a, tab, cnt, P);
     else
-        hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), shm, st, a, tab, cnt, P);
+        hipLaunchKernelGGL((k_fedavg_pipe<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a, tab, cnt, P);
 }
 
 template <typename Y, typename X, class CP, int E, int S, int U, bool NT>
@@ -2194,15 +2002,26 @@ constexpr int64_t kPipeMinClientBytes = 160ll << 20;
 template <typename Y>
 inline bool pipe_pays(int64_t P) { return P * (int64_t)sizeof(Y) >= kPipeMinClientBytes; }
 
-template <typename Y, typename X, class CP, int E>
-void launch_fedavg_small(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
-                         hipStream_t st);
-
 template <class CP> struct is_sf_rule : std::false_type {};
 template <typename Y, typename X> struct is_sf_rule<CWSUM<Y, X>> : std::true_type {};
 template <typename T_> struct is_sf_rule<CRUN<T_>> : std::true_type {};
 
-// The tunable geometries are instantiated for the fp32 hot path only; other dtypes use the default.
+// The product's geometry for the fp32 hot path (fp32 / bf16 updates into an fp32 aggregate), both builds.
+template <typename Y, typename X, class CP, int E>
+void launch_fedavg_default(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
+                           hipStream_t st) {
+    if (!pipe_pays<Y>(P)) return launch_fedavg_small<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st);
+    // measured best on MI355X (profiles/r01_microbench.md): 4 x 16-B strips per lane, the next
+    // client's strips in flight (pipelined), cached loads, non-temporal aggregate stores.
+    // bf16 clients: strips of 4 elements (8-B loads, 16-B f32 stores), 8 per lane, so every wave
+    // store is one contiguous 1 KiB — +3.5 % at K = 64, +7 % at K = 8 (profiles/r02_narrow_probe.log)
+    if constexpr (sizeof(Y) < sizeof(X) && E % 2 == 0)
+        return launch_fedavg_pipe<Y, X, CP, E / 2, 8, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
+    else
+        return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
+}
+
+// The tunable geometries (probe build) are instantiated for the fp32 hot path only; other dtypes use the default.
 template <typename Y, typename X, class CP, int E>
 void launch_fedavg_vec(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, bool first, bool int_first,
                        hipStream_t st) {
@@ -2215,60 +2034,9 @@ void launch_fedavg_vec(X* a, const ClientTable<typename CP::S>& tab, int cnt, in
     }
     if constexpr (tunable) {
 #ifdef FEDAGG_PROBES
-        const int block_log = g_cfg.block_log, strips = g_cfg.strips, unroll = g_cfg.unroll, nt = g_cfg.nt;
-        const int lanetab = g_cfg.lanetab, nt_store = g_cfg.nt_store, tilemap = g_cfg.tilemap;
-        const int key = (block_log == 9 ? 20000 : block_log == 10 ? 30000 : 0) + lanetab * 10000 + strips * 100 +
-                        unroll * 2 + nt;
-        // the default settings select the product's size-dependent geometry (FA_TUNE_AUTO_GEOM 0 forces them)
-        if (g_cfg.auto_geom && key == 4 * 100 + 0 && nt_store == 1 && tilemap == 0 && !pipe_pays<Y>(P))
-            return launch_fedavg_small<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st);
-        if constexpr (sizeof(Y) < sizeof(X) && E % 2 == 0) {
-            if (g_cfg.narrow && key == 4 * 100 + 0 && nt_store == 1 && tilemap == 0)
-                return launch_fedavg_pipe<Y, X, CP, E / 2, 8, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
-        }
-        switch (key) {
-#define FA_GEOM(S_, U_, NT_) \
-    case S_ * 100 + U_ * 2 + NT_: return launch_fedavg_geom<Y, X, CP, E, S_, U_, NT_>(a, tab, cnt, P, first, int_first, st);
-            FA_GEOM(1, 4, 0) FA_GEOM(1, 8, 0) FA_GEOM(1, 16, 0) FA_GEOM(2, 4, 0) FA_GEOM(2, 8, 0) FA_GEOM(2, 16, 0)
-            FA_GEOM(4, 1, 0) FA_GEOM(4, 2, 0) FA_GEOM(4, 4, 0) FA_GEOM(8, 1, 0) FA_GEOM(8, 2, 0) FA_GEOM(16, 1, 0)
-            FA_GEOM(1, 8, 1) FA_GEOM(4, 2, 1) FA_GEOM(8, 1, 1)
-            case 2 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 2, false, false>(a, tab, cnt, P, first, int_first, st);
-            case 4 * 100 + 0:
-                if (nt_store == 1 && tilemap > 0) {
-                    switch (tilemap) {
-#define FA_MAP(R_) \
-    case R_: return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 1, R_>(a, tab, cnt, P, first, int_first, st);
-                        FA_MAP(2) FA_MAP(4) FA_MAP(8) FA_MAP(16) FA_MAP(32)
-#undef FA_MAP
-                        default: break;
-                    }
-                }
-                if (nt_store == 1) return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
-                if (nt_store == 2) return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 2>(a, tab, cnt, P, first, int_first, st);
-                return launch_fedavg_pipe<Y, X, CP, E, 4, false, false>(a, tab, cnt, P, first, int_first, st);
-            case 8 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 8, false, false>(a, tab, cnt, P, first, int_first, st);
-            case 4 * 100 + 1: return launch_fedavg_pipe<Y, X, CP, E, 4, true, false>(a, tab, cnt, P, first, int_first, st);
-            case 20000 + 4 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, 512>(a, tab, cnt, P, first, int_first, st);
-            case 30000 + 4 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, 1024>(a, tab, cnt, P, first, int_first, st);
-            case 20000 + 8 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 8, false, false, 512>(a, tab, cnt, P, first, int_first, st);
-            case 30000 + 2 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 2, false, false, 1024>(a, tab, cnt, P, first, int_first, st);
-            case 10000 + 2 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 2, false, true>(a, tab, cnt, P, first, int_first, st);
-            case 10000 + 4 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 4, false, true>(a, tab, cnt, P, first, int_first, st);
-            case 10000 + 8 * 100 + 0: return launch_fedavg_pipe<Y, X, CP, E, 8, false, true>(a, tab, cnt, P, first, int_first, st);
-#undef FA_GEOM
-            default: break;
-        }
-#else
-        if (!pipe_pays<Y>(P)) return launch_fedavg_small<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st);
-        // measured best on MI355X (profiles/r01_microbench.md): 4 x 16-B strips per lane, the next
-        // client's strips in flight (pipelined), cached loads, non-temporal aggregate stores.
-        // bf16 clients: strips of 4 elements (8-B loads, 16-B f32 stores), 8 per lane, so every wave
-        // store is one contiguous 1 KiB — +3.5 % at K = 64, +7 % at K = 8 (profiles/r02_narrow_probe.log)
-        if constexpr (sizeof(Y) < sizeof(X) && E % 2 == 0)
-            return launch_fedavg_pipe<Y, X, CP, E / 2, 8, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
-        else
-            return launch_fedavg_pipe<Y, X, CP, E, 4, false, false, kBlock, 1>(a, tab, cnt, P, first, int_first, st);
+        if (probe_fedavg_geometry<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st)) return;
 #endif
+        return launch_fedavg_default<Y, X, CP, E>(a, tab, cnt, P, first, int_first, st);
     }
     launch_fedavg_geom<Y, X, CP, E, 1, kUnroll, false>(a, tab, cnt, P, first, int_first, st);
 }
@@ -2315,71 +2083,6 @@ int launch_fedopt_one(const OptBuffers& b, const OptScalars& s, const ClientTabl
                       int64_t P, bool first, bool final_, hipStream_t st) {
     g_kernel = E == 4 ? "k_fedopt_c" : "k_fedopt";
     const dim3 grid((unsigned)grid_for(P, E));
-#ifdef FEDAGG_PROBES
-    // the probe variants exist for the configs[3] shapes only (fp32 updates over an fp32 or fp64
-    // model, vector path); every other combination runs the product kernels in the probe build too
-    constexpr bool probe_combo = E == 4 && std::is_same<Y, float>::value &&
-                                 (std::is_same<OLD, float>::value || std::is_same<OLD, double>::value);
-    if constexpr (probe_combo) {
-        if (final_ && g_cfg.opt_g && std::is_same<OLD, double>::value) {
-            if (b.m_out_f64 != 1 || b.v_out_f32 || b.out_f32 || !b.v_in || b.v_in_f32)
-                return fail(FA_EINVAL, "fa_tune OPT_G probe: fp64 m / v / model out, fp64 v in");
-            const int G = g_cfg.opt_g;
-            const dim3 gg((unsigned)((P + 4 * 512 * G - 1) / (4 * 512 * G)));
-            switch (G) {
-#define FA_OPTG(G_) \
-    case G_: if (first) hipLaunchKernelGGL((k_fedopt_cg<Y, OLD, PG, true, NT, G_>), gg, dim3(kBlock), 0, st, b, s, tab, cnt, P); \
-             else hipLaunchKernelGGL((k_fedopt_cg<Y, OLD, PG, false, NT, G_>), gg, dim3(kBlock), 0, st, b, s, tab, cnt, P); break;
-                FA_OPTG(1) FA_OPTG(2) FA_OPTG(4)
-#undef FA_OPTG
-                default: return fail(FA_EINVAL, "fa_tune OPT_G: 1, 2 or 4 tiles per wave");
-            }
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && g_cfg.opt_burst) {
-            if (b.m_out_f64 != 1) return fail(FA_EINVAL, "fa_tune OPT_BURST probe: fp64 m out");
-            const int G = g_cfg.opt_burst;
-            const dim3 gb((unsigned)((P + 4 * 512 * G - 1) / (4 * 512 * G)));   // a ragged last group is skipped
-            switch (G) {
-#define FA_BURST(G_) \
-    case G_: hipLaunchKernelGGL((k_fedopt_mixg<Y, OLD, typename PG::S, NT, G_>), gb, dim3(kBlock), 0, st, b, tab, cnt, P); break;
-                FA_BURST(1) FA_BURST(2) FA_BURST(4)
-#undef FA_BURST
-                default: return fail(FA_EINVAL, "fa_tune OPT_BURST: 1, 2 or 4 tiles per wave");
-            }
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && g_cfg.opt_win_period > 0 && !g_cfg.opt_win_prod) {
-            if (b.m_out_f64 != 1) return fail(FA_EINVAL, "fa_tune OPT_WIN probe: fp64 m out");
-            const dim3 gw((unsigned)((P + 4 * 512 - 1) / (4 * 512)));   // a ragged last tile is skipped
-            hipLaunchKernelGGL((k_fedopt_mixw<Y, OLD, typename PG::S, NT>), gw, dim3(kBlock), 0, st, b, tab, cnt, P,
-                               (uint32_t)g_cfg.opt_win_period.load(), (uint32_t)g_cfg.opt_win_w.load(), g_cfg.opt_win_mode.load());
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && g_cfg.opt_mix) {
-            const dim3 gm((unsigned)((P + 4 * 512 - 1) / (4 * 512)));   // a ragged last tile is skipped
-            hipLaunchKernelGGL((k_fedopt_mix<Y, OLD, typename PG::S, NT>), gm, dim3(kBlock), 0, st, b, tab, cnt, P);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && g_cfg.opt_nostore) {
-            hipLaunchKernelGGL((k_fedopt<Y, OLD, PG, E, true, true, NT, true>), grid, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && g_cfg.opt_coal == 1) {   // 2 pairs per lane (a 256-element wave tile)
-            hipLaunchKernelGGL((k_fedopt_c<Y, OLD, PG, true, true, NT, 1, 2>), grid, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && !g_cfg.opt_coal) {    // the per-lane 4-element strip map (r01), for A/B
-            if (g_cfg.opt_store == 1)
-                hipLaunchKernelGGL((k_fedopt<Y, OLD, PG, E, true, true, NT, false, 1>), grid, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            else if (g_cfg.opt_store == 2)
-                hipLaunchKernelGGL((k_fedopt<Y, OLD, PG, E, true, true, NT, false, 2>), grid, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            else
-                hipLaunchKernelGGL((k_fedopt<Y, OLD, PG, E, true, true, NT>), grid, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-    }
-#endif
     if constexpr (E == 4) {
         // wave-coalesced element map, 4 pairs per lane (512-element wave tiles), non-temporal state /
         // model stores: +3-6 % over the per-lane strip map on configs[3], bit-identical
@@ -2387,69 +2090,13 @@ int launch_fedopt_one(const OptBuffers& b, const OptScalars& s, const ClientTabl
         // fp16 updates: one dword per pair)
         const dim3 g4((unsigned)((P + 4 * 512 - 1) / (4 * 512)));
 #ifdef FEDAGG_PROBES
-        if constexpr (std::is_same<Y, bf16>::value && std::is_same<OLD, double>::value && std::is_same<PG, CF64>::value) {
-            if (g_cfg.opt_quad) {                    // configs[4]'s wave kernels with the quad element map
-                g_kernel = "k_fedopt_cq";
-                if (first && final_) hipLaunchKernelGGL((k_fedopt_cq<Y, OLD, PG, true, true, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-                else if (first) hipLaunchKernelGGL((k_fedopt_cq<Y, OLD, PG, true, false, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-                else if (final_) hipLaunchKernelGGL((k_fedopt_cq<Y, OLD, PG, false, true, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-                else hipLaunchKernelGGL((k_fedopt_cq<Y, OLD, PG, false, false, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-                return check_launch("fa_fedopt_step: kernel launch");
-            }
-        }
-        const unsigned shm = (unsigned)g_cfg.lds_kib * 1024u;
-        if constexpr (probe_combo) {
-        if (first && final_ && g_cfg.opt_mv) {
-            if (P % (4 * 512) || b.m_in_f64 != 1 || b.m_out_f64 != 1 || !b.v_in)
-                return fail(FA_EINVAL, "fa_tune OPT_MV probe: P %% 2048 == 0, fp64 m in and out, v given");
-            hipLaunchKernelGGL((k_fedopt_c_mv<Y, OLD, PG, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-        if (first && final_ && !(g_cfg.opt_win_period > 0 && g_cfg.opt_win_prod)) {   // (a window: below)
-            switch (g_cfg.wpe) {
-#define FA_WPE(W_) \
-    case W_: hipLaunchKernelGGL((k_fedopt_c_w<Y, OLD, PG, true, true, NT, 1, 4, kUnroll / 2, W_>), g4, dim3(kBlock), shm, st, b, s, tab, cnt, P); \
-        return check_launch("fa_fedopt_step: kernel launch");
-                FA_WPE(6) FA_WPE(8)
-#undef FA_WPE
-                default:
-                    if (shm) {
-                        hipLaunchKernelGGL((k_fedopt_c<Y, OLD, PG, true, true, NT, 1, 4>), g4, dim3(kBlock), shm, st, b, s, tab, cnt, P);
-                        return check_launch("fa_fedopt_step: kernel launch");
-                    }
-                    break;                                  // the product's own choice below
-            }
-        }
-        }
+        int prc = FA_OK;
+        if (probe_fedopt_launch<Y, OLD, PG, NT>(b, s, tab, cnt, P, first, final_, g4, st, prc)) return prc;
 #endif
         if (first && final_) {
             StoreWindow sw = opt_store_window<Y, OLD, PG, NT>(b, cnt, P);
 #ifdef FEDAGG_PROBES
-            if (g_cfg.opt_win_period < 0) sw = StoreWindow{};                                 // A/B: no window
-            else if (g_cfg.opt_win_period > 0 && g_cfg.opt_win_prod) sw = StoreWindow{(uint32_t)g_cfg.opt_win_period.load(),
-                                                                                          (uint32_t)g_cfg.opt_win_w.load()};
-#endif
-#ifdef FEDAGG_PROBES
-            if constexpr (probe_combo) {
-                if (sw.period && g_cfg.opt_win_prod == 1 && (g_cfg.wpe == 6 || g_cfg.wpe == 7)) {
-                    if (g_cfg.wpe == 6)
-                        hipLaunchKernelGGL((k_fedopt_cw_w<Y, OLD, PG, NT, 6>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, sw.period, sw.w);
-                    else
-                        hipLaunchKernelGGL((k_fedopt_cw_w<Y, OLD, PG, NT, 7>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, sw.period, sw.w);
-                    return check_launch("fa_fedopt_step: kernel launch");
-                }
-                if (sw.period && g_cfg.opt_win_prod == 3) {
-                    const dim3 g2((unsigned)((P + 4 * 256 - 1) / (4 * 256)));
-                    hipLaunchKernelGGL((k_fedopt_cw2<Y, OLD, PG, NT>), g2, dim3(kBlock), 0, st, b, s, tab, cnt, P, sw.period, sw.w);
-                    return check_launch("fa_fedopt_step: kernel launch");
-                }
-                if (sw.period && g_cfg.opt_win_prod == 2) {
-                    if (b.m_out_f64 != 1 || b.v_out_f32 || b.out_f32 || (b.v_in && b.v_in_f32))
-                        return fail(FA_EINVAL, "fa_tune OPT_WIN_PROD 2: fp64 m / v / model out");
-                    hipLaunchKernelGGL((k_fedopt_cgw<Y, OLD, PG, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, sw.period, sw.w);
-                    return check_launch("fa_fedopt_step: kernel launch");
-                }
-            }
+            probe_opt_window(sw);
 #endif
             if (sw.period) {
                 g_kernel = "k_fedopt_cw";
@@ -2457,16 +2104,6 @@ int launch_fedopt_one(const OptBuffers& b, const OptScalars& s, const ClientTabl
                 return check_launch("fa_fedopt_step: kernel launch");
             }
         }
-#ifdef FEDAGG_PROBES
-        if (!final_ && g_cfg.opt_win_period > 0 && g_cfg.opt_win_prod) {
-            const uint32_t per = (uint32_t)g_cfg.opt_win_period.load(), w = (uint32_t)g_cfg.opt_win_w.load();
-            if (first)
-                hipLaunchKernelGGL((k_fedopt_cwp<Y, OLD, PG, true, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, per, w);
-            else
-                hipLaunchKernelGGL((k_fedopt_cwp<Y, OLD, PG, false, NT>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P, per, w);
-            return check_launch("fa_fedopt_step: kernel launch");
-        }
-#endif
         if (first && final_) hipLaunchKernelGGL((k_fedopt_c<Y, OLD, PG, true, true, NT, 1, 4>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
         else if (first) hipLaunchKernelGGL((k_fedopt_c<Y, OLD, PG, true, false, NT, 1, 4>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
         else if (final_) hipLaunchKernelGGL((k_fedopt_c<Y, OLD, PG, false, true, NT, 1, 4>), g4, dim3(kBlock), 0, st, b, s, tab, cnt, P);
@@ -2502,16 +2139,6 @@ int launch_fedopt(const OptBuffers& b, const OptScalars& s, const void* const* u
         }
         const bool last = k0 + cnt >= K;
         const bool fin = last && final_all;
-#ifdef FEDAGG_PROBES
-        if constexpr (std::is_same<Y, float>::value && (std::is_same<OLD, float>::value || std::is_same<OLD, double>::value))
-        if (vec && !g_cfg.opt_nt) {
-            int rc = launch_fedopt_one<Y, OLD, PG, 4, false>(b, s, tab, cnt, P, first, fin, st);
-            if (rc) return rc;
-            first = false;
-            k0 += cnt;
-            continue;
-        }
-#endif
         int rc = vec ? launch_fedopt_one<Y, OLD, PG, 4, true>(b, s, tab, cnt, P, first, fin, st)
                      : launch_fedopt_one<Y, OLD, PG, 1, false>(b, s, tab, cnt, P, first, fin, st);
         if (rc) return rc;
@@ -3212,11 +2839,6 @@ int fa_tune(int knob, int value) {
             if (value < 0 || value > 64) return fail(FA_EINVAL, "fa_tune: grid blocks per CU must be 0..64");
             g_cfg.grid_per_cu = value;
             return FA_OK;
-        case FA_TUNE_TILEMAP:
-            if (value != 0 && value != 2 && value != 4 && value != 8 && value != 16 && value != 32)
-                return fail(FA_EINVAL, "fa_tune: tile map 0 (identity) or runs of 2, 4, 8, 16, 32 tiles per XCD");
-            g_cfg.tilemap = value;
-            return FA_OK;
         case FA_TUNE_LANETAB:
             g_cfg.lanetab = value ? 1 : 0;
             return FA_OK;
@@ -3226,41 +2848,14 @@ int fa_tune(int knob, int value) {
         case FA_TUNE_FASTDIV64:
             g_cfg.fastdiv64 = value ? 1 : 0;
             return FA_OK;
-        case FA_TUNE_OPT_NT:
-            g_cfg.opt_nt = value ? 1 : 0;
-            return FA_OK;
-        case FA_TUNE_OPT_NOSTORE:
-            g_cfg.opt_nostore = value ? 1 : 0;
-            return FA_OK;
-        case FA_TUNE_OPT_COAL:
-            if (value < 0 || value > 2)
-                return fail(FA_EINVAL, "fa_tune: FedOpt map 0 (strip), 1 (coalesced, 2 pairs/lane), 2 (4 pairs/lane: product)");
-            g_cfg.opt_coal = value;
-            return FA_OK;
-        case FA_TUNE_OPT_STORE:
-            if (value < 0 || value > 2) return fail(FA_EINVAL, "fa_tune: FedOpt store mode 0 (plain), 1 (nt) or 2 (sc1)");
-            g_cfg.opt_store = value;
-            return FA_OK;
         case FA_TUNE_NARROW:
             g_cfg.narrow = value ? 1 : 0;
-            return FA_OK;
-        case FA_TUNE_LDS:
-            if (value < 0 || value > 64) return fail(FA_EINVAL, "fa_tune: occupancy-probe LDS 0..64 KiB per workgroup");
-            g_cfg.lds_kib = value;
             return FA_OK;
         case FA_TUNE_AUTO_GEOM:
             g_cfg.auto_geom = value ? 1 : 0;
             return FA_OK;
-        case FA_TUNE_OPT_MV:
-            g_cfg.opt_mv = value ? 1 : 0;
-            return FA_OK;
         case FA_TUNE_OPT_MIX:
             g_cfg.opt_mix = value ? 1 : 0;
-            return FA_OK;
-        case FA_TUNE_OPT_G:
-            if (value != 0 && value != 1 && value != 2 && value != 4)
-                return fail(FA_EINVAL, "fa_tune: burst-store product probe 0 (off), 1, 2 or 4 tiles per wave");
-            g_cfg.opt_g = value;
             return FA_OK;
         case FA_TUNE_OPT_WIN_PERIOD:
             if (value != 0 && value != -1 && (value < 64 || value > (1 << 24)))
@@ -3276,12 +2871,8 @@ int fa_tune(int knob, int value) {
             g_cfg.opt_win_mode = value;
             return FA_OK;
         case FA_TUNE_OPT_WIN_PROD:
-            if (value < 0 || value > 3)
-                return fail(FA_EINVAL, "fa_tune: OPT_WIN_PROD 0 (pattern probe), 1 (k_fedopt_cw), 2 (k_fedopt_cgw), 3 (k_fedopt_cw2)");
+            if (value != 0 && value != 1) return fail(FA_EINVAL, "fa_tune: OPT_WIN_PROD 0 (pattern probe) or 1 (k_fedopt_cw)");
             g_cfg.opt_win_prod = value;
-            return FA_OK;
-        case FA_TUNE_OPT_QUAD:
-            g_cfg.opt_quad = value ? 1 : 0;
             return FA_OK;
         case FA_TUNE_AVG_WIN_PERIOD:
             if (value != 0 && value != -1 && (value < 64 || value > (1 << 24)))
@@ -3295,16 +2886,6 @@ int fa_tune(int knob, int value) {
         case FA_TUNE_AVG_WIN_MODE:
             if (value < 0 || value > 2) return fail(FA_EINVAL, "fa_tune: store-window mode 0, 1 or 2");
             g_cfg.avg_win_mode = value;
-            return FA_OK;
-        case FA_TUNE_OPT_BURST:
-            if (value != 0 && value != 1 && value != 2 && value != 4)
-                return fail(FA_EINVAL, "fa_tune: burst-store probe 0 (off), 1, 2 or 4 tiles per wave");
-            g_cfg.opt_burst = value;
-            return FA_OK;
-        case FA_TUNE_WPE:
-            if (value != 0 && value != 5 && value != 6 && value != 7 && value != 8)
-                return fail(FA_EINVAL, "fa_tune: waves per SIMD 0 (compiler's choice), 5, 6, 7 or 8");
-            g_cfg.wpe = value;
             return FA_OK;
         default:
             return fail(FA_EINVAL, "fa_tune: unknown knob %d", knob);
@@ -3359,7 +2940,7 @@ int fa_stream_read(const void* src, int64_t bytes, void* sink, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const u32x4* s4 = static_cast<const u32x4*>(src);
     u32x4* k4 = static_cast<u32x4*>(sink);
-    // loads in flight per lane (fa_tune FA_TUNE_UNROLL reused for this probe: 4, 8 or 16)
+    // loads in flight per lane (fa_tune FA_TUNE_READ: 4, 8 or 16)
     switch (g_cfg.read_per_lane) {
         case 4: hipLaunchKernelGGL(k_stream_read<4>, dim3((unsigned)((n16 + kBlock * 4 - 1) / (kBlock * 4))), blk, 0, st, s4, n16, k4); break;
         case 8: hipLaunchKernelGGL(k_stream_read<8>, dim3((unsigned)((n16 + kBlock * 8 - 1) / (kBlock * 8))), blk, 0, st, s4, n16, k4); break;

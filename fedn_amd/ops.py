@@ -397,21 +397,8 @@ def stream_read_sink(src):
     return torch.empty(max(1, blocks) * 16, dtype=torch.uint8, device=src.device)
 
 
-_KNOBS = {"strips": _abi.FA_TUNE_STRIPS, "unroll": _abi.FA_TUNE_UNROLL, "nt": _abi.FA_TUNE_NT,
-          "fastdiv": _abi.FA_TUNE_FASTDIV, "lanetab": _abi.FA_TUNE_LANETAB,
-          "grid": _abi.FA_TUNE_GRID, "read": _abi.FA_TUNE_READ,
-          "block": _abi.FA_TUNE_BLOCK, "sum_nostore": _abi.FA_TUNE_SUM_NOSTORE,
-          "nt_store": _abi.FA_TUNE_NT_STORE, "fastdiv64": _abi.FA_TUNE_FASTDIV64,
-          "tilemap": _abi.FA_TUNE_TILEMAP, "opt_nt": _abi.FA_TUNE_OPT_NT, "opt_nostore": _abi.FA_TUNE_OPT_NOSTORE,
-          "opt_store": _abi.FA_TUNE_OPT_STORE, "opt_coal": _abi.FA_TUNE_OPT_COAL, "narrow": _abi.FA_TUNE_NARROW,
-          "lds": _abi.FA_TUNE_LDS, "wpe": _abi.FA_TUNE_WPE,
-          "opt_mv": _abi.FA_TUNE_OPT_MV, "auto_geom": _abi.FA_TUNE_AUTO_GEOM,
-          "opt_mix": _abi.FA_TUNE_OPT_MIX, "opt_burst": _abi.FA_TUNE_OPT_BURST,
-          "opt_g": _abi.FA_TUNE_OPT_G, "opt_win_period": _abi.FA_TUNE_OPT_WIN_PERIOD, "opt_win_w": _abi.FA_TUNE_OPT_WIN_W,
-          "opt_win_mode": _abi.FA_TUNE_OPT_WIN_MODE, "avg_win_period": _abi.FA_TUNE_AVG_WIN_PERIOD,
-          "avg_win_w": _abi.FA_TUNE_AVG_WIN_W, "avg_win_mode": _abi.FA_TUNE_AVG_WIN_MODE,
-          "opt_win_prod": _abi.FA_TUNE_OPT_WIN_PROD,
-          "opt_quad": _abi.FA_TUNE_OPT_QUAD}
+# tune(strips=...) names: _abi's FA_TUNE_* constants in lower case without the prefix
+_KNOBS = {name[len("FA_TUNE_"):].lower(): value for name, value in vars(_abi).items() if name.startswith("FA_TUNE_")}
 
 
 def tune(**knobs):

@@ -29,77 +29,59 @@ int fa_stream_copy(void* dst, const void* src, int64_t bytes, void* stream);
  * kernel but one add per element: the access-pattern ceiling of fa_fedavg_fold.        */
 int fa_stream_sum(float* out, const float* const* bufs, int K, int64_t P, void* stream);
 
-/* Launch-geometry knobs of the fp32 FedAvg kernel (process-global; measurement and
- * tuning only, results are identical for every setting):
- *   FA_TUNE_STRIPS  16-B strips per lane (1 | 2 | 4 | 8 | 16)
- *   FA_TUNE_UNROLL  clients loaded before folding (1 | 2 | 4 | 8 | 16)
- *   (instantiated pairs: see launch_fedavg_vec; other pairs fall back to 1 x 8)
- *   FA_TUNE_NT      non-temporal loads of the client buffers (0 | 1)
- *   FA_TUNE_FASTDIV fp32 t/N via the exact RN64(1/N) product (1, default) or IEEE
- *                   division (0); both are correctly rounded
- *   FA_TUNE_LANETAB pipelined kernel (unroll 0) reads the client table from registers
- *                   via v_readlane (1) or by scalar loads (0)
- *   FA_TUNE_GRID    pipelined kernel: 0 = one 16-KiB-per-client tile per workgroup,
- *                   n = persistent grid of n workgroups per CU sweeping tiles        */
-enum fa_tune_knob { FA_TUNE_STRIPS = 0, FA_TUNE_UNROLL = 1, FA_TUNE_NT = 2, FA_TUNE_FASTDIV = 3, FA_TUNE_LANETAB = 4,
-                    FA_TUNE_GRID = 5, FA_TUNE_READ = 6 /* fa_stream_read loads per lane: 4 | 8 | 16 */,
-                    FA_TUNE_BLOCK = 7 /* pipelined kernel workgroup size 256 | 512 | 1024 */,
-                    FA_TUNE_SUM_NOSTORE = 8 /* fa_stream_sum probe: 1 = skip the store (reads + adds only) */,
-                    FA_TUNE_NT_STORE = 9 /* aggregate stores: 0 plain, 1 non-temporal, 2 write-through (sc1) */,
-                    FA_TUNE_FASTDIV64 = 10 /* fp64 t/N via RN64(1/N) + two exact Markstein corrections (1,
-                                              default) or IEEE division (0); both correctly rounded */,
-                    FA_TUNE_TILEMAP = 11 /* pipelined kernel: workgroup -> tile order, 0 identity or runs of
-                                            R = 2 | 4 | 8 | 16 | 32 consecutive tiles per XCD */,
-                    FA_TUNE_OPT_NT = 12 /* FedOpt client loads non-temporal (1, product) or cached (0) */,
-                    FA_TUNE_OPT_NOSTORE = 13 /* FedOpt FIRST|FINAL launch: 1 = skip the stores (reads + math) */,
-                    FA_TUNE_OPT_STORE = 14 /* FedOpt FIRST|FINAL, strip map (OPT_COAL 0): stores 0 plain, 1 nt, 2 sc1 */,
-                    FA_TUNE_OPT_COAL = 15 /* FedOpt FIRST|FINAL element map: 2 = the product's (k_fedopt_c, 4
-                                             coalesced pairs per lane, nt stores), 1 = 2 pairs per lane,
-                                             0 = the r01 per-lane 4-element strip map */,
-                    FA_TUNE_NARROW = 16 /* bf16 -> f32 FedAvg: 1 = the product's 8-B client strips / 16-B
-                                           aggregate strips (4 elements, 8 strips per lane: every wave store
-                                           one contiguous 1 KiB), 0 = r01's 16-B client strips (8 elements,
-                                           4 per lane) */,
-                    FA_TUNE_LDS = 17 /* occupancy probe: KiB of (unused) dynamic LDS per workgroup of the fold
-                                        and FedOpt kernels, 0..64 */,
-                    FA_TUNE_WPE = 18 /* occupancy probe: fp32 fold / FedOpt FIRST|FINAL kernels compiled for at
-                                        least W waves per SIMD (0 = compiler's choice, 5, 6, 8) */,
-                    FA_TUNE_OPT_MV = 19 /* layout probe, FedOpt FIRST|FINAL steady state: 1 = fp64 m and v
-                                           interleaved per 512-element wave tile in ONE buffer passed as
-                                           m_in / m_out (2P doubles each; P % 2048 == 0) */,
-                    FA_TUNE_AUTO_GEOM = 20 /* 1 (default) = with the default geometry knobs, the product's
-                                              size-dependent choice (4-strip pipelined kernel only for client
-                                              buffers >= 160 MiB, else 1 strip x 4/8 clients ahead); 0 = the
-                                              knobs as set, at every size */,
-                    FA_TUNE_OPT_MIX = 21 /* FedOpt FIRST|FINAL, access-pattern probe: 1 = k_fedopt_c's exact loads
-                                            and stores with one add per value instead of the arithmetic
-                                            (results are NOT the reference's; a ragged last 2048-element
-                                            tile is skipped) */,
-                    FA_TUNE_OPT_BURST = 22 /* FedOpt FIRST|FINAL, burst-store probe (fp64 m out): G = 1, 2 or 4
-                                              wave tiles per wave with k_fedopt_mix's loads, the new v / out / m
-                                              of all G held in registers and stored together after the last
-                                              tile's reads (0 = off; a ragged last group is skipped) */,
-                    FA_TUNE_OPT_G = 23 /* FedOpt FINAL launches over an fp64 model with fp64 state out: the
-                                          product arithmetic with G = 1, 2 or 4 wave tiles per wave and their
-                                          v / out / m stored after the last tile's reads (0 = off) */,
-                    FA_TUNE_OPT_WIN_PERIOD = 24 /* FedOpt FIRST|FINAL, clock-windowed store probe (fp64 m out):
-                                                k_fedopt_mix's pattern with every store issued only while the
-                                                100 MHz reference clock mod value < OPT_WIN_W
-                                                (period in 10-ns ticks, 64 .. 2^24; 0 = off) */,
-                    FA_TUNE_OPT_WIN_W = 25 /* the store window in 10-ns ticks */,
-                    FA_TUNE_OPT_WIN_MODE = 26 /* 0: gate the stores only; 1: also start a tile's reads outside
-                                                 the window; 2: also every client batch's reads */,
-                    FA_TUNE_AVG_WIN_PERIOD = 27 /* FedAvg fp32 k_fedavg_pipe (the headline instantiation): its
-                                                   store window — 0 = the product's own (avg_store_window),
-                                                   -1 = none, > 0 = this period with AVG_WIN_W / _MODE */,
-                    FA_TUNE_AVG_WIN_W = 28,
-                    FA_TUNE_AVG_WIN_MODE = 29,
-                    FA_TUNE_OPT_WIN_PROD = 30 /* 1: OPT_WIN_PERIOD / _W apply to the product step (k_fedopt_cw,
-                                                 bit-identical) instead of the pattern probe; OPT_WIN_PERIOD 0 =
-                                                 the product's own window (opt_store_window), -1 = none */,
-                    FA_TUNE_OPT_QUAD = 31 /* FedOpt over bf16 updates, fp64 old, fp64 pg (configs[4]'s waves):
-                                             1 = k_fedopt_cq, lane L owning 4-element quads at lane stride 4
-                                             (dwordx2 client loads) instead of the product's pairs */ };
+/* The knobs of fa_tune (process-global; measurement and tuning only). Every setting computes the
+ * reference's bits except OPT_MIX and OPT_WIN_PERIOD > 0 without OPT_WIN_PROD, which run access-
+ * pattern probes. fa_tune answers FA_EINVAL for an unknown knob or a value outside the ranges below.
+ *
+ * Launch geometry of the fp32 / bf16 -> fp32 FedAvg fold (the sweep of tools/microbench.py):
+ *   STRIPS x UNROLL x NT: see probe_fedavg_geometry in fedagg.hip for the instantiated
+ *   combinations; any other runs 1 strip x 8 clients ahead.                                    */
+enum fa_tune_knob {
+    FA_TUNE_STRIPS = 0 /* 16-B strips per lane: 1 | 2 | 4 (default) | 8 | 16 */,
+    FA_TUNE_UNROLL = 1 /* clients loaded before folding: 1 | 2 | 4 | 8 | 16 (k_fedavg), or 0 (default) =
+                          the pipelined kernel k_fedavg_pipe */,
+    FA_TUNE_NT = 2 /* non-temporal loads of the client buffers (0 default | 1) */,
+    FA_TUNE_FASTDIV = 3 /* fp32 t/N via the exact RN64(1/N) product (1, default) or IEEE division (0);
+                           both are correctly rounded */,
+    FA_TUNE_LANETAB = 4 /* pipelined kernel reads the client table from registers via v_readlane (1) or
+                           by scalar loads (0, default) */,
+    FA_TUNE_GRID = 5 /* pipelined kernel: 0 (default) = one tile per workgroup, n <= 64 = a persistent
+                        grid of n workgroups per CU sweeping the tiles */,
+    FA_TUNE_READ = 6 /* fa_stream_read loads per lane: 4 | 8 | 16 (default) */,
+    FA_TUNE_BLOCK = 7 /* pipelined kernel workgroup size 256 (default) | 512 | 1024 */,
+    FA_TUNE_SUM_NOSTORE = 8 /* fa_stream_sum: 1 = skip the store (reads + adds only) */,
+    FA_TUNE_NT_STORE = 9 /* aggregate stores of the 4-strip pipelined kernel and fa_stream_sum: 0 plain,
+                            1 non-temporal (default), 2 write-through (sc1) */,
+    FA_TUNE_FASTDIV64 = 10 /* fp64 t/N via RN64(1/N) + two exact Markstein corrections (1, default) or
+                              IEEE division (0); both correctly rounded */,
+    FA_TUNE_NARROW = 11 /* bf16 -> f32 FedAvg: 1 (default) = the product's 8-B client strips / 16-B
+                           aggregate strips (4 elements, 8 strips per lane: every wave store one
+                           contiguous 1 KiB), 0 = 16-B client strips (8 elements, 4 per lane) */,
+    FA_TUNE_AUTO_GEOM = 12 /* 1 (default) = with the default geometry knobs, the product's size-dependent
+                              choice (pipelined kernel only for client buffers >= 160 MiB, else 1 strip
+                              x 4/8 clients ahead); 0 = the knobs as set, at every size */,
+    FA_TUNE_OPT_MIX = 13 /* FedOpt FIRST|FINAL, fp32 updates over an fp32 / fp64 model: 1 = k_fedopt_c's
+                            exact loads and stores with one add per value instead of the arithmetic
+                            (k_fedopt_mix; results are NOT the reference's; a ragged last 2048-element
+                            tile is skipped) */,
+    FA_TUNE_OPT_WIN_PERIOD = 14 /* FedOpt store window, in 10-ns ticks of the 100 MHz reference clock
+                                   (64 .. 2^24): stores are issued only while clock mod period <
+                                   OPT_WIN_W. Without OPT_WIN_PROD: k_fedopt_mix's pattern, windowed
+                                   (k_fedopt_mixw; fp64 m out). With it: see OPT_WIN_PROD.
+                                   0 (default) = the product's own window, -1 = none */,
+    FA_TUNE_OPT_WIN_W = 15 /* the store window in 10-ns ticks */,
+    FA_TUNE_OPT_WIN_MODE = 16 /* k_fedopt_mixw: 0 gate the stores only; 1 also start a tile's reads
+                                 outside the window; 2 also every client batch's reads */,
+    FA_TUNE_AVG_WIN_PERIOD = 17 /* FedAvg fp32 k_fedavg_pipe (the headline instantiation), its store
+                                   window: 0 (default) = the product's own (avg_store_window), -1 =
+                                   none, > 0 = this period with AVG_WIN_W / _MODE, also on the
+                                   continuation launches of K > 64 */,
+    FA_TUNE_AVG_WIN_W = 18,
+    FA_TUNE_AVG_WIN_MODE = 19,
+    FA_TUNE_OPT_WIN_PROD = 20 /* 1: OPT_WIN_PERIOD / _W apply to the product step (k_fedopt_cw, bit-
+                                 identical; a first or middle launch of a multi-launch round runs
+                                 k_fedopt_cwp) instead of the pattern probe (0, default) */
+};
 int fa_tune(int knob, int value);
 int64_t fa_stream_read_blocks(int64_t bytes);
 int fa_stream_read(const void* src, int64_t bytes, void* sink, void* stream);

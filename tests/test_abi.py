@@ -46,6 +46,24 @@ def test_probe_library_exports_both_headers():
     assert _abi.load_probe().fa_abi_version() == _abi.ABI_VERSION
 
 
+def test_knob_numbering_has_one_truth():
+    """enum fa_tune_knob (fedagg_probe.h), _abi's FA_TUNE_* constants and ops.tune's names are one
+    set, numbered 0..n-1 without a gap; fa_tune refuses the first number past it."""
+    from fedn_amd import ops
+    src = re.sub(r"/\*.*?\*/", "", open(PROBE_HEADER).read(), flags=re.S)
+    body = re.search(r"enum\s+fa_tune_knob\s*\{(.*?)\}", src, flags=re.S).group(1)
+    header = {name: int(value) for name, value in re.findall(r"\b(FA_TUNE_[A-Z0-9_]+)\s*=\s*(-?\d+)", body)}
+    assert len(header) == len(re.findall(r"\bFA_TUNE_", body)), "an enumerator without an explicit value"
+    assert header == {k: v for k, v in vars(_abi).items() if k.startswith("FA_TUNE_")}
+    assert sorted(header.values()) == list(range(len(header)))
+    assert {"FA_TUNE_" + k.upper(): v for k, v in ops._KNOBS.items()} == header
+    lib = _abi.load_probe()
+    assert lib.fa_tune(len(header), 0) == _abi.FA_EINVAL and lib.fa_tune(-1, 0) == _abi.FA_EINVAL
+    for bad in (-1, 2, 3):
+        assert lib.fa_tune(_abi.FA_TUNE_OPT_WIN_PROD, bad) == _abi.FA_EINVAL
+    assert lib.fa_tune(_abi.FA_TUNE_OPT_WIN_PROD, 0) == _abi.FA_OK
+
+
 def test_promote_table():
     lib = _abi.load()
     P = lib.fa_promote

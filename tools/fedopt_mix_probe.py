@@ -33,8 +33,6 @@ def main():
     ap.add_argument("--params", type=int, default=2048 * 170898)      # ~350 M, whole 2048-element tiles
     ap.add_argument("--clients", type=int, default=32)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--burst", default="1,2,4", help="burst-store probe G values (tiles per wave), '' = none")
-    ap.add_argument("--opt-g", default="1,2,4", help="product step with G tiles per wave (fa_tune OPT_G), '' = none")
     ap.add_argument("--win", default="", help="clock-windowed store probe: period_ticks:window_ticks:mode,... "
                     "(fa_tune OPT_WIN_*: stores only while the 100 MHz clock mod period < window)")
     a = ap.parse_args()
@@ -63,24 +61,7 @@ def main():
     src = torch.empty(1 << 30, dtype=torch.float32, device=dev).fill_(1.0)
     dst = torch.empty_like(src)
     res = {}
-    bursts = [int(x) for x in a.burst.split(",") if x]
     wins = [tuple(int(v) for v in x.split(":")) for x in a.win.split(",") if x]
-    gs = [int(x) for x in a.opt_g.split(",") if x]
-    # the product arithmetic with G tiles per wave (fa_tune OPT_G): bit-identical to k_fedopt_c?
-    exact = {}
-    if gs:
-        fn = phases["steady"][0]
-        ops.tune(opt_g=0)
-        fn()
-        torch.cuda.synchronize()
-        ref_out = (o2.clone(), m_o.clone(), v_o.clone())
-        for g in gs:
-            ops.tune(opt_g=g)
-            o2.zero_(); m_o.zero_(); v_o.zero_()
-            fn()
-            torch.cuda.synchronize()
-            exact[g] = all(torch.equal(x.view(torch.int64), y.view(torch.int64)) for x, y in zip((o2, m_o, v_o), ref_out))
-        ops.tune(opt_g=0)
     for _ in range(a.reps):
         for name, (fn, _b) in phases.items():
             for mix in (0, 1):
@@ -88,20 +69,6 @@ def main():
                 fn()
                 res.setdefault((name, mix), []).append(median_ms(fn))
             ops.tune(opt_mix=0)
-            for g in gs:                          # the product step with G tiles per wave
-                if name != "steady":
-                    continue
-                ops.tune(opt_g=g)
-                fn()
-                res.setdefault((name, f"g{g}"), []).append(median_ms(fn))
-            ops.tune(opt_g=0)
-            for g in bursts:                      # the burst-store probe: G tiles per wave, stores after
-                if name != "steady":
-                    continue
-                ops.tune(opt_burst=g)
-                fn()
-                res.setdefault((name, f"burst{g}"), []).append(median_ms(fn))
-            ops.tune(opt_burst=0)
             for lg, w, mode in wins:              # stores confined to a chip-wide clock window
                 if name != "steady":
                     continue
@@ -123,17 +90,8 @@ def main():
                           "product_frac_of_copy": round(b / prod / 1e6 / copy_gbs, 4),
                           "reps_product": [round(x, 4) for x in res[(name, 0)]],
                           "reps_pattern": [round(x, 4) for x in res[(name, 1)]],
-                          **{f"burst{g}_ms": round(float(np.median(res[(name, f'burst{g}')])), 4)
-                             for g in bursts if (name, f"burst{g}") in res},
-                          **{f"burst{g}_frac_of_peak": round(b / float(np.median(res[(name, f'burst{g}')])) / 1e6 / PEAK, 4)
-                             for g in bursts if (name, f"burst{g}") in res},
-                          **{f"g{g}_ms": round(float(np.median(res[(name, f'g{g}')])), 4)
-                             for g in gs if (name, f"g{g}") in res},
-                          **{f"g{g}_reps": [round(x, 4) for x in res[(name, f'g{g}')]]
-                             for g in gs if (name, f"g{g}") in res},
                           **{f"win{lg}_{w}_{m}_ms": round(float(np.median(res[(name, f'win{lg}_{w}_{m}')])), 4)
-                             for lg, w, m in wins if (name, f"win{lg}_{w}_{m}") in res},
-                          **({f"g{g}_bit_exact": exact[g] for g in gs} if name == "steady" else {})}), flush=True)
+                             for lg, w, m in wins if (name, f"win{lg}_{w}_{m}") in res}}), flush=True)
     print(json.dumps({"copy_GBps": round(copy_gbs, 1), "reps_ms": [round(x, 4) for x in res[("copy", 0)]]}))
 
 

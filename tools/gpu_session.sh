@@ -132,14 +132,14 @@ for s in $STEPS; do
       echo "upload100mfile rc=0"; grep '"what"' "$OUT/upload100m_file.log" | cut -c1-600 ;;
     winprobe)
       # FedAdam steady state with the chip's stores confined to a common clock window (probe library)
-      timeout -k 10 600 python tools/fedopt_mix_probe.py --burst "" --opt-g "" \
+      timeout -k 10 600 python tools/fedopt_mix_probe.py \
         --win "${FEDN_AMD_WIN:-8192:1200:0,8191:1200:0,8192:1200:2,10000:1400:0,12000:1600:0,14000:2000:0,16384:2400:0,12000:1000:0,12000:2400:0}" \
         > "$OUT/winprobe.log" 2>&1; rc=$?
       echo "winprobe rc=$rc"; cut -c1-1200 "$OUT/winprobe.log" | tail -3; [ $rc -eq 0 ] || exit $rc ;;
     optwin)
       # FedAdam through the product step with / without the chip-wide store window (probe library)
       timeout -k 10 900 python tools/fedopt_window_probe.py ${FEDN_AMD_OPTWIN:+--winprod "$FEDN_AMD_OPTWIN"} \
-        ${FEDN_AMD_OPTWINCG:+--wincg "$FEDN_AMD_OPTWINCG"} ${FEDN_AMD_OPTWINK:+--clients "$FEDN_AMD_OPTWINK"} ${FEDN_AMD_OPTWPE:+--wpe "$FEDN_AMD_OPTWPE"} ${FEDN_AMD_OPTCW2:+--wincw2 "$FEDN_AMD_OPTCW2"} > "$OUT/optwin.log" 2>&1; rc=$?
+        ${FEDN_AMD_OPTWINK:+--clients "$FEDN_AMD_OPTWINK"} > "$OUT/optwin.log" 2>&1; rc=$?
       echo "optwin rc=$rc"; cut -c1-900 "$OUT/optwin.log" | grep -v amdgpu.ids | tail -6; [ $rc -eq 0 ] || exit $rc ;;
     avgwin)
       # FedAvg's fold (64 and 8 x 100 M fp32) with its stores in a chip-wide clock window (probe library)

@@ -19,14 +19,12 @@ from fedn_amd import _abi, ops  # noqa: E402
 from tools.microbench import timed  # noqa: E402
 
 K = 64
-STRIPS, UNROLL, AUTO_GEOM = 0, 1, 20
 GEOMS = {"product": None, "s1_u4": (1, 4), "s1_u8": (1, 8), "s1_u16": (1, 16), "s2_u4": (2, 4), "s2_u8": (2, 8),
          "pipe_s4": (4, 0)}
 
 
 def main():
     _abi.load()
-    probe = _abi.load_probe()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(2)
     ns = [int(v) for v in np.random.default_rng(2).integers(1, 5001, K)]
@@ -43,17 +41,13 @@ def main():
             agg = torch.empty(P, device=dev)
             with _abi.use_probe():
                 if geom is None:
-                    probe.fa_tune(AUTO_GEOM, 1)
-                    probe.fa_tune(STRIPS, 4)
-                    probe.fa_tune(UNROLL, 0)
+                    ops.tune(auto_geom=1, strips=4, unroll=0)
                 else:
-                    probe.fa_tune(AUTO_GEOM, 0)
-                    probe.fa_tune(STRIPS, geom[0])
-                    probe.fa_tune(UNROLL, geom[1])
+                    ops.tune(auto_geom=0, strips=geom[0], unroll=geom[1])
                 ms, _ = timed(lambda: ops.fedavg_fold(agg, views, ns, Ns, init=True), reps=20, warm=3)
-                probe.fa_tune(AUTO_GEOM, 1)
-                probe.fa_tune(STRIPS, 4)
-                probe.fa_tune(UNROLL, 0)
+                if geom is not None and ops.last_kernel() != ("k_fedavg" if geom[1] else "k_fedavg_pipe"):
+                    raise SystemExit(f"{name}: ran {ops.last_kernel()}, not the geometry asked for")
+                ops.tune(auto_geom=1, strips=4, unroll=0)
             same = bool(torch.equal(agg.view(torch.int32), want.view(torch.int32)))
             row[name] = {"ms": round(ms, 4), "frac": round((K * P * 4 + P * 4) / ms / 8e9, 3), "bit_identical": same}
         print(json.dumps(row), flush=True)
