@@ -756,14 +756,129 @@ k_fedavg_pipe(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const 
     fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP>(agg, tab, K, P);
 }
 
+// Store-window mode 3, "parked" (a first launch, INIT): no workgroup idles for the
+// window. The grid is the resident workgroups, each sweeping tiles blockIdx.x + i * gridDim.x. A
+// finished tile's results are parked in LDS (each lane its own 16-B pieces, piece s of lane l at
+// [s * BLK + l]: a lane reads back only what it wrote, so no barrier) and the workgroup goes
+// straight on to its next tile; the parked tile is stored when a poll of the clock, once per
+// client pair, finds the window open — or, still parked when the next tile is finished, behind
+// the bounded wait of modes 0-2. The whole sweep is one stream of (tile, client) loads through the
+// a / b ping-pong, so the next tile's client 0 is in flight while this tile's last client is
+// folded. The last parked tile is stored at once (nothing is left to read); the ragged tile, the
+// last of its workgroup, goes through k_fedavg_tail, all its lanes (the same arithmetic per element).
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS>
+__device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const ClientTable<typename CP::S>& tab, const int K,
+                                                 const int64_t P, const uint32_t period, const uint32_t win_w) {
+    using V = typename CP::V;
+    static_assert(E * sizeof(X) == 16, "one 16-B piece per strip");
+    __shared__ u32x4 park[S * BLK];
+    constexpr int64_t kTile = (int64_t)BLK * S * E;
+    const int64_t ntiles = (P + kTile - 1) / kTile, nfull = P / kTile;   // at most one ragged tile follows the whole ones
+    V x[S][E];
+    Y a[S][E], b[S][E];
+    int64_t t = blockIdx.x, parked = -1;                                 // the tile in hand, the tile in LDS
+    int k = 0;
+    // addresses as a uniform strip base + the lane's 32-bit byte offset: no address registers to
+    // wait for while the other buffer's loads are in flight
+    const uint32_t lane_y = threadIdx.x * (uint32_t)(E * sizeof(Y)), lane_x = threadIdx.x * (uint32_t)(E * sizeof(X));
+    auto load = [&](int64_t tt, int kk, Y (&y)[S][E]) {
+        const char* base = static_cast<const char*>(tab.ptr[kk]) + tt * (kTile * (int64_t)sizeof(Y));
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+            strip_load<Y, E, false>(reinterpret_cast<const Y*>(base + (int64_t)s * BLK * E * sizeof(Y) + lane_y), y[s]);
+    };
+    auto flush = [&]() {
+        char* base = reinterpret_cast<char*>(agg) + parked * (kTile * (int64_t)sizeof(X));
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            X xo[E];
+            const u32x4 w = park[s * BLK + threadIdx.x];
+            __builtin_memcpy(xo, &w, 16);
+            strip_store<X, E, NTS>(reinterpret_cast<X*>(base + (int64_t)s * BLK * E * sizeof(X) + lane_x), xo);
+        }
+        parked = -1;
+    };
+    // one client step: `cur` holds client k of tile t
+    auto consume = [&](const Y (&cur)[S][E]) {
+        if (k == 0) {                                                    // x := updates[0] (strip_start's INIT)
+#pragma unroll
+            for (int s = 0; s < S; ++s)
+#pragma unroll
+                for (int e = 0; e < E; ++e) x[s][e] = widen<Y, V>(cur[s][e]);
+        } else {
+            const typename CP::S n = tab.n[k], N = tab.N[k];
+            const double r = tab.r[k];
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                V yv[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) yv[e] = widen<Y, V>(cur[s][e]);
+                fold_strip<CP, E>(x[s], yv, n, N, r);
+            }
+        }
+        if (k == K - 1) {                                                // the tile is finished: park it
+            if (parked >= 0) {
+                wait_write_window(period, win_w);
+                flush();
+            }
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                X xo[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) xo[e] = narrow<X, V>(x[s][e]);
+                u32x4 w;
+                __builtin_memcpy(&w, xo, 16);
+                park[s * BLK + threadIdx.x] = w;
+            }
+            parked = t;
+        } else if ((k & 1) && parked >= 0 && in_write_window(period, win_w)) {
+            flush();
+        }
+    };
+    // the stream's next load is issued before `cur` is consumed. The last step of the sweep, which has
+    // none, is a copy of its own outside the loop: a step that may or may not have loaded would make
+    // every step wait as if it had not (the wait counts are fixed at compile time).
+    auto step = [&](const Y (&cur)[S][E], Y (&nxt)[S][E]) -> bool {
+        int k2 = k + 1;
+        int64_t t2 = t;
+        if (k2 == K) {
+            k2 = 0;
+            t2 += gridDim.x;
+        }
+        if (t2 >= nfull) {
+            consume(cur);
+            return false;
+        }
+        load(t2, k2, nxt);
+        consume(cur);
+        t = t2;
+        k = k2;
+        return true;
+    };
+    if (t < nfull) {
+        load(t, 0, a);
+        while (step(a, b) && step(b, a)) {
+        }
+    }
+    if (parked >= 0) flush();
+    if (nfull < ntiles && nfull % gridDim.x == blockIdx.x)
+        k_fedavg_tail<Y, X, CP, E, S, true, false, BLK>(agg, tab, K, P, nfull * (BLK * S) + threadIdx.x);
+}
+
 // The same fold with every wave's stores inside a chip-wide window of the GPU's 100 MHz clock
 // (avg_store_window): bit-identical, the stores bunched into common bursts.
+// PARK: mode 3, whose LDS no other instantiation carries.
 template <typename Y, typename X, class CP, int E, int S, bool INIT, bool INT_FIRST, bool NT, bool LT, int BLK, int NTS,
-          int MAP>
+          int MAP, bool PARK = false>
 __global__ void __launch_bounds__(BLK)
 k_fedavg_pipe_win(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const int K, const int64_t P,
                   const uint32_t period, const uint32_t win_w, const int win_mode) {
-    fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP, true>(agg, tab, K, P, period, win_w, win_mode);
+    if constexpr (PARK) {
+        static_assert(INIT && !INT_FIRST && !NT && !LT && MAP == 0, "parked stores: first launches of the product geometry");
+        fedavg_park_body<Y, X, CP, E, S, BLK, NTS>(agg, tab, K, P, period, win_w);
+    } else {
+        fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP, true>(agg, tab, K, P, period, win_w, win_mode);
+    }
 }
 
 // ----------------------------------------------------------------------------
@@ -1748,6 +1863,32 @@ StoreWindow opt_store_window(const OptBuffers& b, int K, int64_t P) {
 }
 
 
+// Mode 3 (parked stores, fedavg_park_body) is instantiated for the fp32 geometry's first launch
+template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
+constexpr bool avg_park_geometry = std::is_same<CP, CF32>::value && std::is_same<X, float>::value &&
+                                   std::is_same<Y, float>::value && S * E == 16 && BLK == kBlock && MAP == 0 && !LT && !NT;
+
+// Its grid: kAvgParkPerCu workgroups per CU where the occupancy query allows them (per_cu > 0: that
+// many instead), at most one per tile. The kernel could keep 5 resident (82 VGPRs, 16 KiB LDS), but
+// its waves never idle and keep two clients' loads in flight, and more of them only crowd the
+// memory system: at 64 x 100 M, 2 per CU -2...-3 % against mode 0, 3 per CU -1...-2 %, 4 per CU
+// +2...+4 %, 5 per CU +3 %, 1 per CU slower than mode 0 (profiles/r07_park_sweep.log).
+constexpr int kAvgParkPerCu = 2;
+template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
+int64_t avg_park_grid(int64_t ntiles, int per_cu) {
+    static std::atomic<int> blocks_per_cu{-1};
+    int nb = blocks_per_cu.load(std::memory_order_relaxed);
+    if (nb < 0) {
+        nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                &nb, k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>, BLK, 0) != hipSuccess)
+            nb = 0;
+        blocks_per_cu.store(nb, std::memory_order_relaxed);
+    }
+    nb = per_cu > 0 ? per_cu : std::min(std::max(nb, 1), kAvgParkPerCu);
+    return std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)nb * device_cus()));
+}
+
 // The store window of a first FedAvg launch (k_fedavg_pipe_win), in 10-ns ticks of the reference
 // clock: period 0.45 of the time one round of resident workgroups streams its tiles at 6.4 TB/s,
 // window 15 % — measured (profiles/r05_fedavg_window.log, 100 M fp32, bit-exact, two boxes) at
@@ -1756,6 +1897,7 @@ StoreWindow opt_store_window(const OptBuffers& b, int K, int64_t P) {
 // (write shares over 15 %, models under 2^24 elements, periods under 500 ticks).
 struct AvgWindow {
     uint32_t period = 0, w = 0;
+    int mode = 0;
 };
 template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
 AvgWindow avg_store_window(int K, int64_t P) {
@@ -1777,6 +1919,19 @@ AvgWindow avg_store_window(int K, int64_t P) {
     AvgWindow w;
     w.period = (uint32_t)period;
     w.w = (uint32_t)(0.15 * period);
+    // Parked stores (mode 3), where a wait for the window costs no reading: from 48 fp32 clients (a
+    // write share <= 2 %), period 0.7 of the round of ITS resident workgroups, window 8 % — measured
+    // (profiles/r07_park_sweep.log, 100 M fp32, bit-exact, three boxes) at K = 64: 0.6-0.9 round with
+    // windows of 5-11 % -1.6...-2.8 % against mode 0 above, 1.05 round and longer or windows under
+    // 4 % less or nothing; K = 32 -1.3 % at best, K = 16 0 %, K = 8 +4 %: those keep mode 0.
+    if constexpr (avg_park_geometry<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>) {
+        const double pperiod = 0.7 * period / 0.45 * kAvgParkPerCu / nb;
+        if (K >= 48 && pperiod >= 500 && pperiod <= 20000) {
+            w.period = (uint32_t)pperiod;
+            w.w = (uint32_t)(0.08 * pperiod);
+            w.mode = 3;
+        }
+    }
     return w;
 }
 
@@ -1816,7 +1971,7 @@ bool probe_avg_window_cont(X* a, const ClientTable<typename CP::S>& tab, int cnt
                            dim3 grid, hipStream_t st) {
     if constexpr (std::is_same<CP, CF32>::value && std::is_same<X, float>::value && S * E * (int)sizeof(Y) == 64 &&
                   BLK == kBlock && MAP == 0 && !LT && !NT && NTS == 1) {
-        if (g_cfg.avg_win_period > 0 && !int_first && !first) {
+        if (g_cfg.avg_win_period > 0 && g_cfg.avg_win_mode != 3 && !int_first && !first) {   // (mode 3: first launches only)
             const uint32_t wl = (uint32_t)g_cfg.avg_win_period.load(), ww = (uint32_t)g_cfg.avg_win_w.load();
             g_kernel = "k_fedavg_pipe_win";
             hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, false, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a, tab,
@@ -1949,13 +2104,25 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
     if constexpr (std::is_same<CP, CF32>::value && std::is_same<X, float>::value &&
                   ((std::is_same<Y, float>::value && S * E == 16) || (std::is_same<Y, bf16>::value && S * E == 32)) &&
                   BLK == kBlock && MAP == 0 && !LT && !NT && NTS == 1) {
-        if (first && !int_first && cfg_grid_per_cu() == 0) {
+        if (first && !int_first) {
             AvgWindow w = avg_store_window<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(cnt, P);
-            int wm = 0;
+            int wm = w.mode;
 #ifdef FEDAGG_PROBES
             probe_avg_window(w, wm);
 #endif
-            if (w.period) {
+            // mode 3 (parked stores): its own grid, the resident workgroups (fa_tune GRID n: n per CU)
+            if constexpr (avg_park_geometry<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>) {
+                if (w.period && wm == 3) {
+                    const int64_t all = (strips + (int64_t)BLK * S - 1) / ((int64_t)BLK * S);
+                    const dim3 pgrid((unsigned)avg_park_grid<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(all, cfg_grid_per_cu()));
+                    g_kernel = "k_fedavg_pipe_win";
+                    hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>), pgrid, dim3(BLK),
+                                       0, st, a, tab, cnt, P, w.period, w.w, wm);
+                    return;
+                }
+            }
+            if (wm == 3) wm = 0;                         // not instantiated for this geometry
+            if (w.period && cfg_grid_per_cu() == 0) {
                 g_kernel = "k_fedavg_pipe_win";
                 hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP>), grid, dim3(BLK), 0, st, a,
                                    tab, cnt, P, w.period, w.w, wm);
@@ -2884,7 +3051,7 @@ int fa_tune(int knob, int value) {
             g_cfg.avg_win_w = value;
             return FA_OK;
         case FA_TUNE_AVG_WIN_MODE:
-            if (value < 0 || value > 2) return fail(FA_EINVAL, "fa_tune: store-window mode 0, 1 or 2");
+            if (value < 0 || value > 3) return fail(FA_EINVAL, "fa_tune: store-window mode 0, 1, 2 or 3 (parked)");
             g_cfg.avg_win_mode = value;
             return FA_OK;
         default:

@@ -46,7 +46,8 @@ enum fa_tune_knob {
     FA_TUNE_LANETAB = 4 /* pipelined kernel reads the client table from registers via v_readlane (1) or
                            by scalar loads (0, default) */,
     FA_TUNE_GRID = 5 /* pipelined kernel: 0 (default) = one tile per workgroup, n <= 64 = a persistent
-                        grid of n workgroups per CU sweeping the tiles */,
+                        grid of n workgroups per CU sweeping the tiles; with AVG_WIN_MODE 3 (always a
+                        persistent grid): 0 = its own 2 per CU, n = n per CU */,
     FA_TUNE_READ = 6 /* fa_stream_read loads per lane: 4 | 8 | 16 (default) */,
     FA_TUNE_BLOCK = 7 /* pipelined kernel workgroup size 256 (default) | 512 | 1024 */,
     FA_TUNE_SUM_NOSTORE = 8 /* fa_stream_sum: 1 = skip the store (reads + adds only) */,
@@ -77,7 +78,11 @@ enum fa_tune_knob {
                                    none, > 0 = this period with AVG_WIN_W / _MODE, also on the
                                    continuation launches of K > 64 */,
     FA_TUNE_AVG_WIN_W = 18,
-    FA_TUNE_AVG_WIN_MODE = 19,
+    FA_TUNE_AVG_WIN_MODE = 19 /* 0 gate the stores only; 1 also start a tile's reads outside the window;
+                                 2 also every client pair's reads; 3 "parked" (fp32 updates, first
+                                 launches only; elsewhere it is mode 0): a persistent grid whose
+                                 workgroups park a finished tile in LDS, read on, and store it when
+                                 the window opens */,
     FA_TUNE_OPT_WIN_PROD = 20 /* 1: OPT_WIN_PERIOD / _W apply to the product step (k_fedopt_cw, bit-
                                  identical; a first or middle launch of a multi-launch round runs
                                  k_fedopt_cwp) instead of the pattern probe (0, default) */
