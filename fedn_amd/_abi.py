@@ -29,7 +29,8 @@ FA_PG_FIRST, FA_PG_FINAL = 1, 2
 (FA_TUNE_STRIPS, FA_TUNE_UNROLL, FA_TUNE_NT, FA_TUNE_FASTDIV, FA_TUNE_LANETAB, FA_TUNE_GRID, FA_TUNE_READ,
  FA_TUNE_BLOCK, FA_TUNE_SUM_NOSTORE, FA_TUNE_NT_STORE, FA_TUNE_FASTDIV64, FA_TUNE_NARROW, FA_TUNE_AUTO_GEOM,
  FA_TUNE_OPT_MIX, FA_TUNE_OPT_WIN_PERIOD, FA_TUNE_OPT_WIN_W, FA_TUNE_OPT_WIN_MODE,
- FA_TUNE_AVG_WIN_PERIOD, FA_TUNE_AVG_WIN_W, FA_TUNE_AVG_WIN_MODE, FA_TUNE_OPT_WIN_PROD) = range(21)
+ FA_TUNE_AVG_WIN_PERIOD, FA_TUNE_AVG_WIN_W, FA_TUNE_AVG_WIN_MODE, FA_TUNE_OPT_WIN_PROD,
+ FA_TUNE_AVG_PARK_DEPTH, FA_TUNE_AVG_PARK_SLOTS) = range(23)
 
 EXPORTS = {
     # name: (restype, argtypes)

@@ -756,47 +756,78 @@ k_fedavg_pipe(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const 
     fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP>(agg, tab, K, P);
 }
 
+// The ring depth and the parked tiles per workgroup the product ships (avg_store_window has the
+// measurements).
+constexpr int kAvgParkDepth = 2, kAvgParkSlots = 2;
+
 // Store-window mode 3, "parked" (a first launch, INIT): no workgroup idles for the
 // window. The grid is the resident workgroups, each sweeping tiles blockIdx.x + i * gridDim.x. A
 // finished tile's results are parked in LDS (each lane its own 16-B pieces, piece s of lane l at
-// [s * BLK + l]: a lane reads back only what it wrote, so no barrier) and the workgroup goes
-// straight on to its next tile; the parked tile is stored when a poll of the clock, once per
-// client pair, finds the window open — or, still parked when the next tile is finished, behind
-// the bounded wait of modes 0-2. The whole sweep is one stream of (tile, client) loads through the
-// a / b ping-pong, so the next tile's client 0 is in flight while this tile's last client is
-// folded. The last parked tile is stored at once (nothing is left to read); the ragged tile, the
-// last of its workgroup, goes through k_fedavg_tail, all its lanes (the same arithmetic per element).
-template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS>
+// [s * BLK + l] of a slot) and the workgroup goes straight on to its next tile. Two compile-time
+// parameters (fa_tune AVG_PARK_DEPTH / _SLOTS): DEPTH client buffers in the load ring, SLOTS parked
+// tiles per workgroup.
+// The sweep is one stream of (tile, client) positions; buffer i holds stream position i mod DEPTH,
+// and the step that consumes a position first issues the loads of the position DEPTH - 1 ahead into
+// the buffer the step before it consumed. The load cursor (lt, lk) runs ahead of the consume cursor
+// (t, k) across tile boundaries, over several tiles where K < DEPTH. What keeps the loads in flight:
+//  - the loop is counted (the workgroup's positions are known up front) and unrolled DEPTH times, so
+//    buffer indices are static and the loop has one exit; the remainder of the stream and the last
+//    DEPTH - 1 steps, which load nothing, are copies of their own behind it. (With an exit in every
+//    step, the compiler's common exit block is also a path back to the loop's head on which a step's
+//    buffer is the newest load, and every wait is sized for that.)
+//  - a strip is one buffer load: the position's base in a scalar descriptor, the strip in the scalar
+//    offset, the lane's offset in a loop-invariant register. (Address registers are taken from the
+//    buffer about to be loaded, and computing them waits for all but one load in flight.)
+// Parked tiles are stored oldest first: all of them when a poll of the clock, once per client pair,
+// finds the window open, the oldest behind the bounded wait when a tile is finished with no slot
+// free, the rest at the end of the sweep. Each wave keeps the FIFO for itself: `oldest` (a tile
+// number, -1 = none; the others follow gridDim.x apart), its slot `head`, and `count`. A lane reads
+// back only what it wrote, so there is still no barrier. Arithmetic, element order per lane, store
+// addresses and store flavour are mode 0's. The ragged tile, the last of its workgroup, goes through
+// k_fedavg_tail, all its lanes (the same arithmetic per element).
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS>
 __device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const ClientTable<typename CP::S>& tab, const int K,
                                                  const int64_t P, const uint32_t period, const uint32_t win_w) {
     using V = typename CP::V;
-    static_assert(E * sizeof(X) == 16, "one 16-B piece per strip");
-    __shared__ u32x4 park[S * BLK];
+    static_assert(E * sizeof(X) == 16 && E * sizeof(Y) == 16, "one 16-B piece per strip");
+    static_assert(DEPTH >= 2 && DEPTH <= 4, "a ring of 2, 3 or 4 client buffers");
+    static_assert((SLOTS == 1 || SLOTS == 2 || SLOTS == 4) && SLOTS * S * BLK * 16 <= 65536, "1, 2 or 4 slots of static LDS");
+    __shared__ u32x4 park[SLOTS][S * BLK];
     constexpr int64_t kTile = (int64_t)BLK * S * E;
     const int64_t ntiles = (P + kTile - 1) / kTile, nfull = P / kTile;   // at most one ragged tile follows the whole ones
+    // this workgroup's whole tiles and stream positions
+    const int64_t mine = (int64_t)blockIdx.x < nfull ? (nfull - blockIdx.x + gridDim.x - 1) / gridDim.x : 0, npos = mine * K;
     V x[S][E];
-    Y a[S][E], b[S][E];
-    int64_t t = blockIdx.x, parked = -1;                                 // the tile in hand, the tile in LDS
-    int k = 0;
-    // addresses as a uniform strip base + the lane's 32-bit byte offset: no address registers to
-    // wait for while the other buffer's loads are in flight
+    Y buf[DEPTH][S][E];
+    int64_t t = blockIdx.x, lt = t, oldest = -1;                         // the tile in hand, the last one loaded from, the FIFO
+    int k = 0, lk = 0, head = 0, count = 0;
     const uint32_t lane_y = threadIdx.x * (uint32_t)(E * sizeof(Y)), lane_x = threadIdx.x * (uint32_t)(E * sizeof(X));
-    auto load = [&](int64_t tt, int kk, Y (&y)[S][E]) {
-        const char* base = static_cast<const char*>(tab.ptr[kk]) + tt * (kTile * (int64_t)sizeof(Y));
+    auto load = [&](int64_t tt, int kk, Y (&y)[S][E]) {                  // tt < nfull: a whole tile, inside the client's buffer
+        char* base = const_cast<char*>(static_cast<const char*>(tab.ptr[kk])) + tt * (kTile * (int64_t)sizeof(Y));
+        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(kTile * sizeof(Y)), 0x00020000);
 #pragma unroll
-        for (int s = 0; s < S; ++s)
-            strip_load<Y, E, false>(reinterpret_cast<const Y*>(base + (int64_t)s * BLK * E * sizeof(Y) + lane_y), y[s]);
+        for (int s = 0; s < S; ++s) {
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_y, s * BLK * E * (int)sizeof(Y), 0);
+            __builtin_memcpy(y[s], &w, 16);
+        }
     };
-    auto flush = [&]() {
-        char* base = reinterpret_cast<char*>(agg) + parked * (kTile * (int64_t)sizeof(X));
+    auto next = [&](int64_t& tt, int& kk) {                              // the stream position after (tt, kk)
+        if (++kk == K) {
+            kk = 0;
+            tt += gridDim.x;
+        }
+    };
+    auto flush = [&]() {                                                 // the oldest parked tile
+        char* base = reinterpret_cast<char*>(agg) + oldest * (kTile * (int64_t)sizeof(X));
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             X xo[E];
-            const u32x4 w = park[s * BLK + threadIdx.x];
+            const u32x4 w = park[head][s * BLK + threadIdx.x];
             __builtin_memcpy(xo, &w, 16);
             strip_store<X, E, NTS>(reinterpret_cast<X*>(base + (int64_t)s * BLK * E * sizeof(X) + lane_x), xo);
         }
-        parked = -1;
+        head = (head + 1) % SLOTS;
+        oldest = --count ? oldest + gridDim.x : -1;
     };
     // one client step: `cur` holds client k of tile t
     auto consume = [&](const Y (&cur)[S][E]) {
@@ -817,10 +848,11 @@ __device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const Clie
             }
         }
         if (k == K - 1) {                                                // the tile is finished: park it
-            if (parked >= 0) {
+            if (count == SLOTS) {                                        // no slot free
                 wait_write_window(period, win_w);
                 flush();
             }
+            const int slot = (head + count) % SLOTS;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 X xo[E];
@@ -828,41 +860,85 @@ __device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const Clie
                 for (int e = 0; e < E; ++e) xo[e] = narrow<X, V>(x[s][e]);
                 u32x4 w;
                 __builtin_memcpy(&w, xo, 16);
-                park[s * BLK + threadIdx.x] = w;
+                park[slot][s * BLK + threadIdx.x] = w;
             }
-            parked = t;
-        } else if ((k & 1) && parked >= 0 && in_write_window(period, win_w)) {
-            flush();
+            if (count++ == 0) oldest = t;
+        } else if ((k & 1) && count > 0 && in_write_window(period, win_w)) {
+            do flush();
+            while (count > 0);
         }
+        next(t, k);
     };
-    // the stream's next load is issued before `cur` is consumed. The last step of the sweep, which has
-    // none, is a copy of its own outside the loop: a step that may or may not have loaded would make
-    // every step wait as if it had not (the wait counts are fixed at compile time).
-    auto step = [&](const Y (&cur)[S][E], Y (&nxt)[S][E]) -> bool {
-        int k2 = k + 1;
-        int64_t t2 = t;
-        if (k2 == K) {
-            k2 = 0;
-            t2 += gridDim.x;
-        }
-        if (t2 >= nfull) {
-            consume(cur);
-            return false;
-        }
-        load(t2, k2, nxt);
-        consume(cur);
-        t = t2;
-        k = k2;
-        return true;
+    // a step of the full ring: the load DEPTH - 1 positions ahead is issued before buf[I] is consumed
+    auto step = [&](auto ix) {
+        constexpr int I = decltype(ix)::value;
+        next(lt, lk);
+        load(lt, lk, buf[(I + DEPTH - 1) % DEPTH]);
+        consume(buf[I]);
     };
-    if (t < nfull) {
-        load(t, 0, a);
-        while (step(a, b) && step(b, a)) {
+    // the last DEPTH - 1 positions, all loaded, from buf[I] on
+    auto drain = [&](auto ix) {
+        constexpr int I = decltype(ix)::value;
+#pragma unroll
+        for (int j = 0; j < DEPTH - 1; ++j) consume(buf[(I + j) % DEPTH]);
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2 % DEPTH>;
+    using I3 = std::integral_constant<int, 3 % DEPTH>;
+    if (npos >= DEPTH - 1) {
+        load(t, 0, buf[0]);                                              // DEPTH - 1 positions before the first consume
+#pragma unroll
+        for (int j = 1; j < DEPTH - 1; ++j) {
+            next(lt, lk);
+            load(lt, lk, buf[j]);
         }
+        const int64_t nstep = npos - (DEPTH - 1);                        // steps that load
+        for (int64_t i = nstep / DEPTH; i > 0; --i) {
+            step(I0{});
+            step(I1{});
+            if constexpr (DEPTH > 2) step(I2{});
+            if constexpr (DEPTH > 3) step(I3{});
+        }
+        const int rem = (int)(nstep % DEPTH);
+        if (rem == 0) {
+            drain(I0{});
+        } else {
+            step(I0{});
+            if (DEPTH == 2 || rem == 1) {
+                drain(I1{});
+            } else {
+                step(I1{});
+                if (DEPTH == 3 || rem == 2) {
+                    drain(I2{});
+                } else {
+                    step(I2{});
+                    drain(I3{});
+                }
+            }
+        }
+    } else if (npos > 0) {                                               // a stream shorter than the ring: 1 or 2 positions
+        load(t, 0, buf[0]);
+        if (npos > 1) {
+            next(lt, lk);
+            load(lt, lk, buf[1]);
+        }
+        consume(buf[0]);
+        if (npos > 1) consume(buf[1]);
     }
-    if (parked >= 0) flush();
+    while (count > 0) flush();
     if (nfull < ntiles && nfull % gridDim.x == blockIdx.x)
         k_fedavg_tail<Y, X, CP, E, S, true, false, BLK>(agg, tab, K, P, nfull * (BLK * S) + threadIdx.x);
+}
+
+// The parked fold at any (DEPTH, SLOTS), for the probe library: a kernel template of its own, so that
+// the window kernels keep their names (profiles/pmc_traffic.json is keyed on them). The launcher
+// reports k_fedavg_pipe_win's family for it.
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS>
+__global__ void __launch_bounds__(BLK)
+k_fedavg_park(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const int K, const int64_t P, const uint32_t period,
+              const uint32_t win_w) {
+    fedavg_park_body<Y, X, CP, E, S, BLK, NTS, DEPTH, SLOTS>(agg, tab, K, P, period, win_w);
 }
 
 // The same fold with every wave's stores inside a chip-wide window of the GPU's 100 MHz clock
@@ -875,7 +951,7 @@ k_fedavg_pipe_win(X* __restrict__ agg, const ClientTable<typename CP::S> tab, co
                   const uint32_t period, const uint32_t win_w, const int win_mode) {
     if constexpr (PARK) {
         static_assert(INIT && !INT_FIRST && !NT && !LT && MAP == 0, "parked stores: first launches of the product geometry");
-        fedavg_park_body<Y, X, CP, E, S, BLK, NTS>(agg, tab, K, P, period, win_w);
+        fedavg_park_body<Y, X, CP, E, S, BLK, NTS, kAvgParkDepth, kAvgParkSlots>(agg, tab, K, P, period, win_w);
     } else {
         fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP, true>(agg, tab, K, P, period, win_w, win_mode);
     }
@@ -1766,7 +1842,7 @@ struct FedAvgCfg {
     std::atomic<int> strips{4}, unroll{0}, lanetab{0}, grid_per_cu{0}, read_per_lane{16}, block_log{8},
         sum_nostore{0}, nt_store{1}, nt{0}, fastdiv{1}, fastdiv64{1}, narrow{1}, auto_geom{1}, opt_mix{0},
         opt_win_period{0}, opt_win_w{0}, opt_win_mode{0}, opt_win_prod{0}, avg_win_period{0}, avg_win_w{0},
-        avg_win_mode{0};
+        avg_win_mode{0}, avg_park_depth{0}, avg_park_slots{0};
 };
 FedAvgCfg g_cfg;
 int cfg_fastdiv() { return g_cfg.fastdiv.load(std::memory_order_relaxed); }
@@ -1869,24 +1945,35 @@ constexpr bool avg_park_geometry = std::is_same<CP, CF32>::value && std::is_same
                                    std::is_same<Y, float>::value && S * E == 16 && BLK == kBlock && MAP == 0 && !LT && !NT;
 
 // Its grid: kAvgParkPerCu workgroups per CU where the occupancy query allows them (per_cu > 0: that
-// many instead), at most one per tile. The kernel could keep 5 resident (82 VGPRs, 16 KiB LDS), but
-// its waves never idle and keep two clients' loads in flight, and more of them only crowd the
-// memory system: at 64 x 100 M, 2 per CU -2...-3 % against mode 0, 3 per CU -1...-2 %, 4 per CU
-// +2...+4 %, 5 per CU +3 %, 1 per CU slower than mode 0 (profiles/r07_park_sweep.log).
-constexpr int kAvgParkPerCu = 2;
-template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
+// many instead), at most one per tile. Its waves never idle and keep the ring's loads in flight
+// behind every consume, and more tile streams than that needs only crowd the memory system: at
+// 64 x 100 M and 2 ring buffers, 1 per CU -0.9...-1.4 % against the round-7 kernel at its own 2 per
+// CU, 2 per CU +1.4...+1.7 %, 3 per CU +4 % and more; 3 or 4 ring buffers +1.7...+6 % at every
+// grid (profiles/r08_ring_sweep.log; the round-7 kernel, whose address arithmetic drained its ring
+// before every load: profiles/r07_park_sweep.log).
+constexpr int kAvgParkPerCu = 1;
+template <auto KERNEL, int BLK>
 int64_t avg_park_grid(int64_t ntiles, int per_cu) {
     static std::atomic<int> blocks_per_cu{-1};
     int nb = blocks_per_cu.load(std::memory_order_relaxed);
     if (nb < 0) {
         nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &nb, k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>, BLK, 0) != hipSuccess)
-            nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL, BLK, 0) != hipSuccess) nb = 0;
         blocks_per_cu.store(nb, std::memory_order_relaxed);
     }
     nb = per_cu > 0 ? per_cu : std::min(std::max(nb, 1), kAvgParkPerCu);
     return std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)nb * device_cus()));
+}
+
+// One parked launch of the product's kernel (the PARK instantiation of k_fedavg_pipe_win).
+template <typename Y, typename X, class CP, int E, int S, bool NT, bool LT, int BLK, int NTS, int MAP>
+void launch_fedavg_park(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, uint32_t period, uint32_t win_w,
+                        int per_cu, hipStream_t st) {
+    constexpr int64_t kTile = (int64_t)BLK * S * E;
+    constexpr auto kernel = k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>;
+    const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>((P + kTile - 1) / kTile, per_cu));
+    g_kernel = "k_fedavg_pipe_win";
+    hipLaunchKernelGGL(kernel, pgrid, dim3(BLK), 0, st, a, tab, cnt, P, period, win_w, 3);
 }
 
 // The store window of a first FedAvg launch (k_fedavg_pipe_win), in 10-ns ticks of the reference
@@ -1919,14 +2006,16 @@ AvgWindow avg_store_window(int K, int64_t P) {
     AvgWindow w;
     w.period = (uint32_t)period;
     w.w = (uint32_t)(0.15 * period);
-    // Parked stores (mode 3), where a wait for the window costs no reading: from 48 fp32 clients (a
-    // write share <= 2 %), period 0.7 of the round of ITS resident workgroups, window 8 % — measured
-    // (profiles/r07_park_sweep.log, 100 M fp32, bit-exact, three boxes) at K = 64: 0.6-0.9 round with
-    // windows of 5-11 % -1.6...-2.8 % against mode 0 above, 1.05 round and longer or windows under
-    // 4 % less or nothing; K = 32 -1.3 % at best, K = 16 0 %, K = 8 +4 %: those keep mode 0.
+    // Parked stores (mode 3), where a wait for the window costs no reading: from 32 fp32 clients (a
+    // write share <= 3 %), kAvgParkDepth ring buffers, kAvgParkSlots parked tiles, period 0.7 of the
+    // round of ITS resident workgroups, window 8 % — measured (profiles/r08_ring_sweep.log, 100 M
+    // fp32, every point bit-exact) at K = 64: -1.1 % against the round-7 kernel's 2 per CU at the same
+    // period and window rule (1 slot -0.9 %; 4 slots at 2.8 rounds and a 4 % window -1.4 %: both
+    // within the session's noise of this one), K = 48 -1.6 %, K = 32 -2.6 % against mode 0 above.
+    // K = 16 0 %, K = 8 +4 % with the round-7 kernel (profiles/r07_park_sweep.log): those keep mode 0.
     if constexpr (avg_park_geometry<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>) {
         const double pperiod = 0.7 * period / 0.45 * kAvgParkPerCu / nb;
-        if (K >= 48 && pperiod >= 500 && pperiod <= 20000) {
+        if (K >= 32 && pperiod >= 500 && pperiod <= 20000) {
             w.period = (uint32_t)pperiod;
             w.w = (uint32_t)(0.08 * pperiod);
             w.mode = 3;
@@ -1962,6 +2051,32 @@ void probe_avg_window(AvgWindow& w, int& mode) {
         w = AvgWindow{(uint32_t)period, (uint32_t)g_cfg.avg_win_w.load()};
         mode = g_cfg.avg_win_mode.load();
     }
+}
+
+// AVG_PARK_DEPTH / _SLOTS on a parked launch: both 0 = the product's kernel (false); otherwise the
+// generalised one (k_fedavg_park; a knob left at 0 is 2 buffers / 1 slot), GRID n = n workgroups per
+// CU. The launcher reports the product's family for it: one fold, one name.
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS>
+bool probe_fedavg_park(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, uint32_t period, uint32_t win_w,
+                       hipStream_t st) {
+    const int depth = g_cfg.avg_park_depth, slots = g_cfg.avg_park_slots;
+    if (!depth && !slots) return false;
+    constexpr int64_t kTile = (int64_t)BLK * S * E;
+    const int64_t ntiles = (P + kTile - 1) / kTile;
+    switch ((depth ? depth : 2) * 10 + (slots ? slots : 1)) {
+#define FA_PARK(D_, S_) \
+    case D_ * 10 + S_: { \
+        constexpr auto kernel = k_fedavg_park<Y, X, CP, E, S, BLK, NTS, D_, S_>; \
+        const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>(ntiles, cfg_grid_per_cu())); \
+        hipLaunchKernelGGL(kernel, pgrid, dim3(BLK), 0, st, a, tab, cnt, P, period, win_w); \
+        break; \
+    }
+        FA_PARK(2, 1) FA_PARK(2, 2) FA_PARK(2, 4) FA_PARK(3, 1) FA_PARK(3, 2) FA_PARK(3, 4) FA_PARK(4, 1) FA_PARK(4, 2) FA_PARK(4, 4)
+#undef FA_PARK
+        default: return false;                           // (fa_tune admits no other value)
+    }
+    g_kernel = "k_fedavg_pipe_win";
+    return true;
 }
 
 // AVG_WIN_PERIOD > 0 on a continuation launch (K > 64) of the fp32 fold: windowed too, which the
@@ -2113,11 +2228,10 @@ void launch_fedavg_pipe(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
             // mode 3 (parked stores): its own grid, the resident workgroups (fa_tune GRID n: n per CU)
             if constexpr (avg_park_geometry<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>) {
                 if (w.period && wm == 3) {
-                    const int64_t all = (strips + (int64_t)BLK * S - 1) / ((int64_t)BLK * S);
-                    const dim3 pgrid((unsigned)avg_park_grid<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(all, cfg_grid_per_cu()));
-                    g_kernel = "k_fedavg_pipe_win";
-                    hipLaunchKernelGGL((k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>), pgrid, dim3(BLK),
-                                       0, st, a, tab, cnt, P, w.period, w.w, wm);
+#ifdef FEDAGG_PROBES
+                    if (probe_fedavg_park<Y, X, CP, E, S, BLK, NTS>(a, tab, cnt, P, w.period, w.w, st)) return;
+#endif
+                    launch_fedavg_park<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>(a, tab, cnt, P, w.period, w.w, cfg_grid_per_cu(), st);
                     return;
                 }
             }
@@ -3053,6 +3167,16 @@ int fa_tune(int knob, int value) {
         case FA_TUNE_AVG_WIN_MODE:
             if (value < 0 || value > 3) return fail(FA_EINVAL, "fa_tune: store-window mode 0, 1, 2 or 3 (parked)");
             g_cfg.avg_win_mode = value;
+            return FA_OK;
+        case FA_TUNE_AVG_PARK_DEPTH:
+            if (value != 0 && value != 2 && value != 3 && value != 4)
+                return fail(FA_EINVAL, "fa_tune: parked ring depth 2, 3 or 4 (0 = the product's)");
+            g_cfg.avg_park_depth = value;
+            return FA_OK;
+        case FA_TUNE_AVG_PARK_SLOTS:
+            if (value != 0 && value != 1 && value != 2 && value != 4)
+                return fail(FA_EINVAL, "fa_tune: parked tiles per workgroup 1, 2 or 4 (0 = the product's)");
+            g_cfg.avg_park_slots = value;
             return FA_OK;
         default:
             return fail(FA_EINVAL, "fa_tune: unknown knob %d", knob);

@@ -47,7 +47,7 @@ enum fa_tune_knob {
                            by scalar loads (0, default) */,
     FA_TUNE_GRID = 5 /* pipelined kernel: 0 (default) = one tile per workgroup, n <= 64 = a persistent
                         grid of n workgroups per CU sweeping the tiles; with AVG_WIN_MODE 3 (always a
-                        persistent grid): 0 = its own 2 per CU, n = n per CU */,
+                        persistent grid): 0 = its own 1 per CU, n = n per CU */,
     FA_TUNE_READ = 6 /* fa_stream_read loads per lane: 4 | 8 | 16 (default) */,
     FA_TUNE_BLOCK = 7 /* pipelined kernel workgroup size 256 (default) | 512 | 1024 */,
     FA_TUNE_SUM_NOSTORE = 8 /* fa_stream_sum: 1 = skip the store (reads + adds only) */,
@@ -85,7 +85,13 @@ enum fa_tune_knob {
                                  the window opens */,
     FA_TUNE_OPT_WIN_PROD = 20 /* 1: OPT_WIN_PERIOD / _W apply to the product step (k_fedopt_cw, bit-
                                  identical; a first or middle launch of a multi-launch round runs
-                                 k_fedopt_cwp) instead of the pattern probe (0, default) */
+                                 k_fedopt_cwp) instead of the pattern probe (0, default) */,
+    FA_TUNE_AVG_PARK_DEPTH = 21 /* AVG_WIN_MODE 3: client buffers in the load ring, 2 | 3 | 4 (the loads of
+                                   that many minus one stream positions stay in flight behind a
+                                   consume); 0 (default) = the product's. With either of the two set,
+                                   the launch is k_fedavg_park's (a knob left at 0: 2 buffers, 1 slot) */,
+    FA_TUNE_AVG_PARK_SLOTS = 22 /* AVG_WIN_MODE 3: parked tiles per workgroup, 1 | 2 | 4 (16 KiB of LDS
+                                   each); 0 (default) = the product's */
 };
 int fa_tune(int knob, int value);
 int64_t fa_stream_read_blocks(int64_t bytes);

@@ -3,12 +3,13 @@ library): the BASELINE workload (64 x 100 M fp32, device-resident, one launch) a
 (8 x 100 M), the product kernel k_fedavg_pipe against the same body whose stores wait for
 clock mod period < window (and, mode 1 / 2, whose reads start / continue outside it; mode 3, "parked":
 a persistent grid that parks a finished tile in LDS and stores it when the window opens, with
-an optional fifth field for the workgroups per CU, 0 = the resident ones).
+optional fifth to seventh fields for the workgroups per CU, the client buffers in its load ring and
+the parked tiles per workgroup, 0 = the product's).
 Interleaved repeats, median ms; each variant's result compared bit for bit with the product's.
 --ceiling adds the same traversal with its stores suppressed (fa_stream_sum, SUM_NOSTORE): what a
 fold whose stores cost nothing would run at on this box.
 
-  python tools/window_probe.py [--win K:period:window:mode[:grid],...] [--ceiling]
+  python tools/window_probe.py [--win K:period:window:mode[:grid[:depth[:slots]]],...] [--ceiling]
 """
 import argparse
 import json
@@ -56,10 +57,12 @@ def main():
         ups = [u.to(torch.bfloat16) for u in ups]
     del base
     allwins = [tuple(int(v) for v in x.split(":")) for x in a.win.split(",") if x]
-    allwins = [w if len(w) == 5 else w + (0,) for w in allwins]      # grid: workgroups per CU (mode 3)
+    allwins = [w + (0,) * (7 - len(w)) for w in allwins]             # mode 3: workgroups per CU, ring depth, slots
 
     def setwin(w):
-        ops.tune(avg_win_period=w[0], avg_win_w=w[1], avg_win_mode=w[2], grid=w[3] if w[2] == 3 else 0)
+        park = w[2] == 3
+        ops.tune(avg_win_period=w[0], avg_win_w=w[1], avg_win_mode=w[2], grid=w[3] if park else 0,
+                 avg_park_depth=w[4] if park else 0, avg_park_slots=w[5] if park else 0)
     agg = torch.empty(P, device=dev)
     for K in (int(k) for k in a.clients.split(",")):
         wins = [w[1:] for w in allwins if w[0] == K]
@@ -72,14 +75,14 @@ def main():
         torch.cuda.synchronize()
         ref = agg.clone()
         exact = {}
-        wins = [(0, 0, 0, 0)] + wins                         # (0, ...): the product's own window
+        wins = [(0, 0, 0, 0, 0, 0)] + wins                   # (0, ...): the product's own window
         for w in wins:
             setwin(w)
             agg.zero_()
             fn()
             torch.cuda.synchronize()
             exact[w] = bool(torch.equal(agg.view(torch.int32), ref.view(torch.int32)))
-        ops.tune(avg_win_period=0, grid=0)
+        ops.tune(avg_win_period=0, grid=0, avg_park_depth=0, avg_park_slots=0)
         res = {}
         for _ in range(a.reps):
             ops.tune(avg_win_period=-1)
@@ -89,14 +92,14 @@ def main():
                 setwin(w)
                 fn()
                 res.setdefault(w, []).append(median_ms(fn))
-            ops.tune(avg_win_period=0, grid=0)
+            ops.tune(avg_win_period=0, grid=0, avg_park_depth=0, avg_park_slots=0)
             if a.ceiling and a.dtype == "f32":
                 ops.tune(sum_nostore=1)
                 ns_fn = lambda: ops.stream_sum(agg, ups[:K])  # noqa: E731
                 ns_fn()
                 res.setdefault("nostore", []).append(median_ms(ns_fn))
                 ops.tune(sum_nostore=0)
-        ops.tune(avg_win_period=0, grid=0)
+        ops.tune(avg_win_period=0, grid=0, avg_park_depth=0, avg_park_slots=0)
         prod = float(np.median(res["product"]))
         out = {"clients": K, "params": P, "dtype": a.dtype, "alg_bytes": alg, "nowin_ms": round(prod, 4),
                "nowin_frac_of_peak": round(alg / prod / 1e6 / PEAK, 4)}
@@ -105,7 +108,8 @@ def main():
             out["sum_nostore"] = {"ms": round(ms, 4), "read_tbps": round(K * P * 4 / ms / 1e9, 3)}
         for w in wins:
             ms = float(np.median(res[w]))
-            name = f"win{w[0]}_{w[1]}_{w[2]}" + (f"_g{w[3]}" if w[3] else "")
+            name = (f"win{w[0]}_{w[1]}_{w[2]}" + (f"_g{w[3]}" if w[3] else "") + (f"_d{w[4]}" if w[4] else "") +
+                    (f"_s{w[5]}" if w[5] else ""))
             out["product_window" if w[0] == 0 else name] = {"ms": round(ms, 4), "frac_of_peak": round(alg / ms / 1e6 / PEAK, 4),
                                                "bit_exact": exact[w]}
         print(json.dumps(out), flush=True)
