@@ -107,6 +107,10 @@ EXPORTS = {
     "fa_host_device_ptr": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "fa_host_register": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
     "fa_host_unregister": (ctypes.c_int, [ctypes.c_void_p]),
+    "fa_trimmed_mean": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
+        ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # K, trim, P, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -118,7 +122,7 @@ PROBE_EXPORTS = {
     "fa_stream_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:
 FA_REL_MASK, FA_REL_ARRIVED, FA_REL_LAUNCHES, FA_REL_MISSES, FA_REL_SEEN, FA_REL_EXPECT = range(6)

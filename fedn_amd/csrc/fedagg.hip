@@ -2429,6 +2429,9 @@ int launch_fedopt(const OptBuffers& b, const OptScalars& s, const void* const* u
     return FA_OK;
 }
 
+// coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
+#include "order_mean.h"
+
 }  // namespace
 
 // ============================================================================
@@ -3082,6 +3085,32 @@ int fa_peer_enable(int dev, int peer) {
     }
     if (e != hipSuccess) return fail(FA_EHIP, "fa_peer_enable(%d -> %d): %s", dev, peer, hipGetErrorString(e));
     return FA_OK;
+}
+
+int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int trim, int64_t P,
+                    void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!out || !updates) return fail(FA_EINVAL, "fa_trimmed_mean: null pointer argument");
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_trimmed_mean: K=%d outside 1..%d", K, kMaxK);
+    if (trim < 0 || 2 * trim >= K) return fail(FA_EINVAL, "fa_trimmed_mean: trim=%d leaves nothing of K=%d", trim, K);
+    if (P < 0) return fail(FA_EINVAL, "fa_trimmed_mean: negative size (P=%lld)", (long long)P);
+    const bool pair = (upd_dtype == FA_F32 && out_dtype == FA_F32) || (upd_dtype == FA_F64 && out_dtype == FA_F64) ||
+                      (upd_dtype == FA_F16 && out_dtype == FA_F16) || (upd_dtype == FA_BF16 && out_dtype == FA_F32) ||
+                      ((upd_dtype == FA_I32 || upd_dtype == FA_I64) && out_dtype == FA_F64);
+    if (!pair)
+        return fail(FA_EDTYPE, "fa_trimmed_mean: unsupported dtype pair (update %d, output %d)", upd_dtype, out_dtype);
+    if (P == 0) return FA_OK;
+    for (int k = 0; k < K; ++k)
+        if (!updates[k]) return fail(FA_EINVAL, "fa_trimmed_mean: updates[%d] is NULL", k);
+    switch (upd_dtype) {
+        case FA_F32: return launch_order_mean<float>(out, updates, K, trim, P, st);
+        case FA_F64: return launch_order_mean<double>(out, updates, K, trim, P, st);
+        case FA_F16: return launch_order_mean<f16>(out, updates, K, trim, P, st);
+        case FA_BF16: return launch_order_mean<bf16>(out, updates, K, trim, P, st);
+        case FA_I32: return launch_order_mean<int32_t>(out, updates, K, trim, P, st);
+        default: return launch_order_mean<int64_t>(out, updates, K, trim, P, st);
+    }
 }
 
 #ifdef FEDAGG_PROBES

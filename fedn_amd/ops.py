@@ -184,6 +184,63 @@ def weighted_sum(acc, updates, w, stream=None):
     return acc
 
 
+MAX_ORDER_K = 64      # clients of one fa_trimmed_mean call (the kernarg table; one sorting network)
+
+
+def order_mean_dtype(upd_dt):
+    """dtype of the trimmed mean / median of updates of torch dtype ``upd_dt``: numpy's
+    ``np.sort(S, 0)[t:K-t].mean(0)`` dtype — the float dtype itself, float64 for integers — and
+    float32 for bf16 (the fp32 rule on exact upcasts)."""
+    if upd_dt in (torch.float32, torch.float64, torch.float16):
+        return upd_dt
+    if upd_dt == torch.bfloat16:
+        return torch.float32
+    if upd_dt in (torch.int32, torch.int64):
+        return torch.float64
+    raise TypeError(f"trimmed_mean: dtype {upd_dt} is not supported")
+
+
+def median_trim(K):
+    """The trim count that makes the trimmed mean the median: the middle value of an odd K, the mean
+    of the two middle values of an even one."""
+    return (K - 1) // 2
+
+
+def trimmed_mean(out, updates, trim, stream=None):
+    """Coordinate-wise trimmed mean on device (``fa_trimmed_mean``): per element, the ``trim``
+    smallest and ``trim`` largest of the K updates' values are dropped (-0 before +0, NaNs last) and
+    the rest averaged in ascending order — ``np.sort(S, 0)[trim:K-trim].mean(0)`` bit for bit.
+
+    out      flat device tensor of :func:`order_mean_dtype` of the updates' dtype (written)
+    updates  1 <= K <= 64 flat device tensors of one dtype and of ``out``'s length
+    trim     0 <= trim, 2 * trim < K
+    """
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"trimmed_mean takes 1..{MAX_ORDER_K} updates, got {K}")
+    P = out.numel()
+    dev = out.device
+    _check_dev("out", out, P, None)
+    upd_dt = updates[0].dtype
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one trimmed_mean call must share a dtype")
+    with _on(dev):
+        st = _stream_handle(out, stream)
+        rc = lib.fa_trimmed_mean(out.data_ptr(), fa_dtype(out), _abi.ptr_array([u.data_ptr() for u in updates]),
+                                 fa_dtype(upd_dt), K, int(trim), P, st)
+    _abi.check(rc)
+    return out
+
+
+def median(out, updates, stream=None):
+    """Coordinate-wise median on device: :func:`trimmed_mean` with ``trim = (K - 1) // 2``
+    (``np.median(S, 0)`` bit for bit)."""
+    return trimmed_mean(out, updates, median_trim(len(updates)), stream)
+
+
 def running_mean(g, m, a, b, T, stream=None):
     """``g = (g*a + m*b)/T`` in place (``fa_running_mean``): one step of the reference's
     incremental server-function example (sf_incremental_aggregation.py:36-37)."""

@@ -1,0 +1,230 @@
+"""Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median.
+
+Unlike the FedAvg fold, which sees one client at a time, an order statistic needs all K updates of a
+round at once: per element, the K values are sorted, the ``trim`` smallest and largest dropped and the
+rest averaged (``fa_trimmed_mean``, kernel ``k_order_mean``). So the pipeline HOLDS the
+round's updates — in HBM while ``budget.HbmBudget`` admits them, on the host otherwise — and
+``result(trim)`` reduces them:
+
+  * every update in HBM: ONE launch per dtype group reads each update once and writes the model;
+  * some updates on the host: the groups are reduced slice by slice. A slice of each host-side update
+    is copied into a reused device ring (one row per such update, two buffers) on the copy stream
+    while the compute stream reduces the previous slice; updates in HBM are addressed in place at
+    ``base + lo``; each slice's result is copied out before its buffer is reused. HBM use is bounded
+    by the budget plus the ring: never an OOM, never a dropped client.
+
+Both rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
+``ops.MAX_ORDER_K`` (64) updates per round.
+
+Stream ordering (the rules DESIGN.md records for fresh HBM, §3.7): a buffer is allocated on the
+stream that first writes it (staged updates and the ring on the copy stream, results on the compute
+stream); the compute
+stream waits for an update's ``ready`` event before the launch that reads it; the copy stream waits
+for the launch that last read a ring buffer before it refills it; everything the launches read is
+held until the result is on the host.
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import ingest, ops, reuse
+from .budget import HbmBudget
+from .ingest import ShardedStagedModel, StagedModel
+from .layout import Layout
+
+# bytes of one update's slice in the ring (host-side updates only): the ring holds
+# 2 x (host-side updates) x SLICE_BYTES
+SLICE_BYTES = 32 << 20
+SLICE_ALIGN = 64              # slice bounds in elements: every slice base stays 16-B aligned
+
+
+class UnsupportedRound(TypeError):
+    """A round the robust rules do not serve: several devices, parameter-sliced staged updates, an
+    androidhelper session, or a dtype ``fa_trimmed_mean`` does not take."""
+
+
+def trim_count(trim_fraction, K):
+    """Values dropped at EACH end of K sorted values: ``floor(trim_fraction * K)``, never more than
+    ``(K - 1) // 2`` (at least one value is kept whatever the product's rounding does)."""
+    import math
+    return max(0, min(math.floor(trim_fraction * K), (K - 1) // 2))
+
+
+def _several_devices():
+    from .aggregators.fedavg import env_devices
+    devs = env_devices()
+    return bool(devs and len(devs) > 1)
+
+
+class RobustPipeline:
+    """Holds one round's updates and reduces them with ``fa_trimmed_mean`` on one device."""
+
+    def __init__(self, device, first, tag=None, budget=None):
+        if _several_devices():
+            raise UnsupportedRound("the robust rules run on one device: FEDN_AMD_DEVICES names several")
+        if isinstance(first, ShardedStagedModel):
+            raise UnsupportedRound("the robust rules run on one device: the update is staged as parameter slices")
+        self.device = torch.device(device)
+        self.layout = first.layout if isinstance(first, StagedModel) else Layout.of([np.asarray(a) for a in first])
+        self._out_dt = {}
+        for dt in self.layout.groups:
+            try:
+                self._out_dt[dt] = ops.order_mean_dtype(ops.torch_dtype(dt))
+            except TypeError as e:
+                raise UnsupportedRound(f"the robust rules take float32 / float64 / float16 / int32 / int64 tensors: {e}") from e
+        self.budget = budget if budget is not None else HbmBudget()
+        self.compute = torch.cuda.current_stream(self.device)
+        self.copy = torch.cuda.Stream(self.device)
+        self.updates = []            # StagedModel (in HBM) or list[np.ndarray] (host-side), FIFO
+        self.tags = []
+        self.host_side = 0           # updates the budget (or a full HBM) left on the host
+        self._h2d, self._kern = [], []
+        self.time_pack = 0.0
+        self.time_d2h = 0.0
+        self.add(first, tag)
+
+    def __len__(self):
+        return len(self.updates)
+
+    # ---- admission -------------------------------------------------------------------
+    def add(self, update, tag=None):
+        """Admit one update: a StagedModel is used in place; host arrays go to HBM now (copy stream)
+        if the budget admits them, else stay on the host. Raises if its layout differs from the
+        round's (the first update's), so the aggregator skips it."""
+        if isinstance(update, ShardedStagedModel):
+            raise UnsupportedRound("the robust rules run on one device: the update is staged as parameter slices")
+        if isinstance(update, StagedModel):
+            self.layout.check_layout(update.layout)
+            if update.dev.device != self.device:
+                raise ValueError(f"staged update is on {update.dev.device}, the round runs on {self.device}")
+            entry = update
+        else:
+            arrays = [np.asarray(a) for a in update]
+            self.layout.check(arrays)
+            entry = self._stage(arrays)
+        self.updates.append(entry)
+        self.tags.append(tag)
+
+    def _stage(self, arrays):
+        parts = [(self.device, self.layout.nbytes)]
+        if self.budget.reserve(parts):
+            try:
+                tic = time.perf_counter()
+                with torch.cuda.device(self.device):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(self.copy)
+                    staged = ingest.stage_arrays(arrays, self.device, self.copy)
+                    b.record(self.copy)
+                self._h2d.append((a, b))
+                self.time_pack += time.perf_counter() - tic
+                return self.budget.hold(staged, parts)
+            except torch.cuda.OutOfMemoryError:
+                self.budget.release(parts)
+        self.host_side += 1
+        return arrays
+
+    # ---- reduction -------------------------------------------------------------------
+    def result(self, trim):
+        """The round's model as host arrays in the layout's shapes (dtypes: ``ops.order_mean_dtype``):
+        per element the mean of the sorted values ``s[trim] .. s[K - trim - 1]``."""
+        K = len(self.updates)
+        if not 1 <= K <= ops.MAX_ORDER_K:
+            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        if trim < 0 or 2 * trim >= K:
+            raise ValueError(f"trim={trim} leaves nothing of {K} updates")
+        out = [None] * len(self.layout.shapes)
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
+                for u in self.updates:
+                    if isinstance(u, StagedModel):
+                        self.compute.wait_event(u.ready)
+                hosts = {dt: self._reduce_group(dt, trim) for dt in self.layout.groups}
+                tic = time.perf_counter()
+                self.compute.synchronize()
+                self.time_d2h += time.perf_counter() - tic
+        except BaseException:
+            # a failed launch: what was enqueued drains before the caller may free anything it reads
+            torch.cuda.synchronize(self.device)
+            raise
+        for dt in self.layout.groups:
+            self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
+        return out
+
+    def _host_flat(self, arrays, dt):
+        """(flat array, element offset in the group) of the non-empty members of group ``dt``."""
+        return [(np.ascontiguousarray(arrays[i]).reshape(-1), off) for i, off in self.layout.members[dt]
+                if self.layout.sizes[i]]
+
+    def _reduce_group(self, dt, trim):
+        n = self.layout.group_elems[dt]
+        tdt, odt = ops.torch_dtype(dt), self._out_dt[dt]
+        host = torch.empty(n, dtype=odt, pin_memory=True)
+        if n == 0:                                   # only empty tensors: no launch
+            return host
+        isz, goff = dt.itemsize, self.layout.group_byte_offset[dt]
+        on_host = [k for k, u in enumerate(self.updates) if not isinstance(u, StagedModel)]
+        if on_host:
+            step = max(SLICE_ALIGN, SLICE_BYTES // isz // SLICE_ALIGN * SLICE_ALIGN)
+        else:
+            step = n                                 # every update in HBM: one launch
+        step = min(step, n)
+        nbuf = 2 if n > step else 1
+        flats = {k: self._host_flat(self.updates[k], dt) for k in on_host}
+        ring = None
+        if on_host:
+            with torch.cuda.stream(self.copy):       # allocated on the stream that writes it
+                ring = reuse.watch(torch.empty((nbuf, len(on_host), step), dtype=tdt, device=self.device), self.copy)
+        outs = [torch.empty(step, dtype=odt, device=self.device) for _ in range(nbuf)]
+        consumed = [None] * nbuf
+        for s, lo in enumerate(range(0, n, step)):
+            hi, b = min(n, lo + step), s % nbuf
+            if on_host:
+                if consumed[b] is not None:
+                    self.copy.wait_event(consumed[b])          # the launch that read this buffer ran
+                h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(self.copy):
+                    h0.record(self.copy)
+                    for r, k in enumerate(on_host):
+                        for flat, off in flats[k]:             # members overlapping [lo, hi)
+                            s0, s1 = max(lo, off), min(hi, off + flat.size)
+                            if s0 < s1:
+                                ring[b, r, s0 - lo:s1 - lo].copy_(torch.from_numpy(flat[s0 - off:s1 - off]),
+                                                                  non_blocking=True)
+                    h1.record(self.copy)
+                self._h2d.append((h0, h1))
+                self.compute.wait_event(h1)
+            views, r = [], 0
+            for u in self.updates:
+                if isinstance(u, StagedModel):
+                    views.append(u.dev[goff + lo * isz:goff + hi * isz].view(tdt))
+                else:
+                    views.append(ring[b, r, :hi - lo])
+                    r += 1
+            k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            k0.record(self.compute)
+            ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
+            k1.record(self.compute)
+            self._kern.append((k0, k1))
+            if on_host:
+                consumed[b] = torch.cuda.Event()
+                consumed[b].record(self.compute)
+            # the result leaves on the compute stream: in order behind its launch and ahead of the
+            # launch that reuses outs[b]
+            host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
+        if ring is not None:
+            ring.record_stream(self.compute)
+        return host
+
+    # ---- bookkeeping -----------------------------------------------------------------
+    def timings(self):
+        """GPU-side H2D and kernel time (s, HIP events) plus host staging and D2H wall time."""
+        torch.cuda.synchronize(self.device)
+        h2d = sum(a.elapsed_time(b) for a, b in self._h2d) / 1e3
+        kern = sum(a.elapsed_time(b) for a, b in self._kern) / 1e3
+        return {"time_h2d": h2d, "time_kernel": kern, "time_pack": self.time_pack, "time_d2h": self.time_d2h}
+
+    def release(self):
+        """Drop the round's updates once nothing enqueued reads them (their HBM returns to the budget)."""
+        torch.cuda.synchronize(self.device)
+        self.updates, self.tags = [], []

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 8
+#define FA_ABI_VERSION 9
 
 /* element type codes */
 enum fa_dtype {
@@ -338,6 +338,29 @@ int fa_peer_enable(int dev, int peer);
 int fa_host_register(void* p, int64_t bytes);
 int fa_host_unregister(void* p);
 int fa_host_device_ptr(const void* host, void** dptr);
+
+/*
+ * fa_trimmed_mean (ABI 9): coordinate-wise trimmed mean of K client updates (Yin et al., 2018), the
+ * median included — a robust, UNWEIGHTED rule: one client cannot move a parameter past the others'.
+ * Per element, the K values of upd_dtype are put in the total order "by value, -0 before +0, every
+ * NaN (either sign, any payload) after +inf, all NaNs equal"; of the ascending sequence s the values
+ * s[trim] .. s[K-trim-1] are kept, and
+ *     out = (((A(s[trim]) + A(s[trim+1])) + ...) + A(s[K-trim-1])) / A(K - 2*trim)
+ * with every add rounded once in the accumulator type A (the sum starts from the first kept value, not
+ * from zero: a kept run of -0 gives -0), an IEEE division, and one rounding to out_dtype. A NaN among
+ * the kept values gives NaN. This equals numpy's np.sort(S, axis=0)[trim:K-trim].mean(axis=0) bit for
+ * bit, and with trim = (K-1)/2 np.median(S, axis=0) (numpy leaves the order of -0 / +0 ties open).
+ *
+ * (upd, out) pairs and A:  (F32,F32) f32   (F64,F64) f64   (F16,F16) f32   (BF16,F32) f32 on exact
+ * upcasts   (I32,F64) / (I64,F64) f64, each kept value converted with one rounding.
+ *
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * trim     0 <= trim and 2*trim < K;  the median is trim = (K - 1) / 2
+ * FA_EINVAL: a null pointer, K or trim out of range, P < 0; FA_EDTYPE: any other dtype pair; FA_OK
+ * for P = 0 — all before any HIP call. fa_last_kernel reports "k_order_mean".
+ */
+int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype,
+                    int K, int trim, int64_t P, void* stream);
 
 #ifdef __cplusplus
 }
