@@ -78,7 +78,10 @@ int fa_abi_version(void);
 const char* fa_last_error(void);
 /* ABI 8: the kernel family the calling thread's last fold / FedOpt launch ran ("k_fedavg",
  * "k_fedavg_pipe", "k_fedavg_pipe_win", "k_fedopt", "k_fedopt_c", "k_fedopt_cw"; "" before any), so a
- * benchmark reports the kernel that ran — e.g. whether the store window was used — not a guess. */
+ * benchmark reports the kernel that ran — e.g. whether the store window was used — not a guess.
+ * fa_weighted_sum and fa_running_mean run the fold's kernels with their own arithmetic and report
+ * them too: "k_fedavg" (a pointer not 16-B aligned, or a client buffer below 160 MiB) or
+ * "k_fedavg_pipe" (at and above it). */
 const char* fa_last_kernel(void);
 
 /*
