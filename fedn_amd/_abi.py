@@ -111,6 +111,11 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
         ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # K, trim, P, stream
+    "fa_pairwise_sqdist_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),   # K, P
+    "fa_pairwise_sqdist": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,    # D, updates, upd_dtype
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
+        ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -120,9 +125,14 @@ PROBE_EXPORTS = {
     "fa_stream_copy": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "fa_stream_read_blocks": (ctypes.c_int64, [ctypes.c_int64]),
     "fa_stream_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "fa_pairwise_sqdist_geometry": (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_int,                                        # upd_dtype, K
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int)]),                                    # tile, R, grid, tiles per flush
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
+PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:
 FA_REL_MASK, FA_REL_ARRIVED, FA_REL_LAUNCHES, FA_REL_MISSES, FA_REL_SEEN, FA_REL_EXPECT = range(6)

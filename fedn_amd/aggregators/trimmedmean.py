@@ -54,6 +54,7 @@ class Aggregator(AggregatorBase):
 
     default_parameters = DEFAULT_PARAMETERS
     parameter_schema = PARAMETER_SCHEMA
+    fraction_parameter = "trim_fraction"      # the one parameter, a float in [0, 0.5) (subclasses rename it)
 
     def __init__(self, update_handler, device=None, hbm_budget=None):
         super().__init__(update_handler)
@@ -65,6 +66,10 @@ class Aggregator(AggregatorBase):
     def trim(self, K, parameters):
         """Values dropped at each end of the K admitted updates' sorted values."""
         return trim_count(parameters["trim_fraction"], K)
+
+    def reduce_round(self, pipe, K, parameters):
+        """The model of the K admitted updates held by ``pipe`` (the rule itself: subclasses override)."""
+        return pipe.result(self.trim(K, parameters))
 
     def combine_models(self, helper=None, delete_models=True, parameters=None):
         self._begin_deletes()
@@ -85,9 +90,9 @@ class Aggregator(AggregatorBase):
         else:
             parameters = {}
         merged = {**self.default_parameters, **parameters}
-        f = merged.get("trim_fraction")
+        f = merged.get(self.fraction_parameter)
         if f is not None and not 0.0 <= f < 0.5:       # (a NaN fails both comparisons)
-            raise InvalidParameterError(f"Parameter trim_fraction must lie in [0, 0.5), got {f}")
+            raise InvalidParameterError(f"Parameter {self.fraction_parameter} must lie in [0, 0.5), got {f}")
         return merged
 
     def _drain(self):
@@ -146,7 +151,7 @@ class Aggregator(AggregatorBase):
             return None, data
         try:
             tic = time.time()
-            model = pipe.result(self.trim(K, parameters))
+            model = self.reduce_round(pipe, K, parameters)
             data["time_model_aggregation"] += time.time() - tic
             data.update(pipe.timings())
         except Exception as e:  # noqa: BLE001 — a failed launch: every update stays in storage

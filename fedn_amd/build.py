@@ -8,6 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "fedagg.hip")
 ORDER_SRC = os.path.join(HERE, "csrc", "order_mean.h")   # k_order_mean (fa_trimmed_mean), included by SRC
+PAIR_SRC = os.path.join(HERE, "csrc", "pair_dist.h")     # k_pair_sqdist (fa_pairwise_sqdist), included by SRC
 HDR = os.path.join(ROOT, "include", "fedagg.h")
 OUT = os.path.join(HERE, "libfedagg.so")
 PROBE_HDR = os.path.join(ROOT, "include", "fedagg_probe.h")
@@ -91,7 +92,7 @@ def build(force=False, verbose=True):
 
 def build_hip(force=False, verbose=True, probe=False):
     out = PROBE_OUT if probe else OUT
-    deps = (SRC, ORDER_SRC, HDR, PROBE_HDR)
+    deps = (SRC, ORDER_SRC, PAIR_SRC, HDR, PROBE_HDR)
     if not force and not _stale(out, *deps):
         return out
     tmp = out + ".tmp"

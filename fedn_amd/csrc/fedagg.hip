@@ -2432,6 +2432,9 @@ int launch_fedopt(const OptBuffers& b, const OptScalars& s, const void* const* u
 // coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
 #include "order_mean.h"
 
+// pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
+#include "pair_dist.h"
+
 }  // namespace
 
 // ============================================================================
@@ -3111,6 +3114,56 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
         case FA_I32: return launch_order_mean<int32_t>(out, updates, K, trim, P, st);
         default: return launch_order_mean<int64_t>(out, updates, K, trim, P, st);
     }
+}
+
+#ifdef FEDAGG_PROBES
+int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                                int* flush_tiles) {
+    g_err[0] = 0;
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_pairwise_sqdist_geometry: K=%d outside 1..%d", K, kMaxK);
+    if (upd_dtype != FA_F32 && upd_dtype != FA_F16 && upd_dtype != FA_BF16 && !pair_family64(upd_dtype))
+        return fail(FA_EDTYPE, "fa_pairwise_sqdist_geometry: unsupported dtype %d", upd_dtype);
+    int te = 0, ft = 0;
+    auto get = [&](auto gm) -> int {
+        te = decltype(gm)::TE;
+        ft = kPairChain / decltype(gm)::PER_TILE;
+        return FA_OK;
+    };
+    if (pair_family64(upd_dtype)) pair_for_kp<double>(K, get);
+    else pair_for_kp<float>(K, get);
+    if (tile_elems) *tile_elems = te;
+    if (chain_terms) *chain_terms = kPairChain;
+    if (max_workgroups) *max_workgroups = kPairGrid;
+    if (flush_tiles) *flush_tiles = ft;
+    return FA_OK;
+}
+#endif  // FEDAGG_PROBES
+
+int64_t fa_pairwise_sqdist_work(int K, int64_t P) {
+    if (K < 1 || K > kMaxK || P < 0) return 0;
+    int64_t n = 0;
+    pair_for_kp<double>(K, [&](auto gm) -> int {        // the f64 family's tile is the smaller one: most workgroups
+        using GM = decltype(gm);
+        n = pair_workgroups(P, GM::TE) * GM::PART;
+        return FA_OK;
+    });
+    return std::max<int64_t>(n, 1);
+}
+
+int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int K, int64_t P, int accumulate,
+                       double* work, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!D || !updates || !work) return fail(FA_EINVAL, "fa_pairwise_sqdist: null pointer argument");
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_pairwise_sqdist: K=%d outside 1..%d", K, kMaxK);
+    if (P < 0) return fail(FA_EINVAL, "fa_pairwise_sqdist: negative size (P=%lld)", (long long)P);
+    const bool f32fam = upd_dtype == FA_F32 || upd_dtype == FA_F16 || upd_dtype == FA_BF16;
+    if (!f32fam && !pair_family64(upd_dtype)) return fail(FA_EDTYPE, "fa_pairwise_sqdist: unsupported dtype %d", upd_dtype);
+    for (int k = 0; k < K && P > 0; ++k)                     // (an empty buffer may be a null pointer)
+        if (!updates[k]) return fail(FA_EINVAL, "fa_pairwise_sqdist: updates[%d] is NULL", k);
+    if (accumulate && (P == 0 || K == 1)) return FA_OK;      // nothing to add: no launch
+    if (f32fam) return launch_pair_sqdist<float>(D, updates, upd_dtype, K, P, accumulate, work, st);
+    return launch_pair_sqdist<double>(D, updates, upd_dtype, K, P, accumulate, work, st);
 }
 
 #ifdef FEDAGG_PROBES

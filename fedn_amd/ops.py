@@ -241,6 +241,78 @@ def median(out, updates, stream=None):
     return trimmed_mean(out, updates, median_trim(len(updates)), stream)
 
 
+_SQDIST_F32 = (torch.float32, torch.float16, torch.bfloat16)
+_SQDIST_F64 = (torch.float64, torch.int32, torch.int64)
+
+
+def sqdist_geometry(dtype, K):
+    """``(TE, R, max workgroups, tiles per flush)`` of ``fa_pairwise_sqdist`` for K updates of ``dtype``:
+    the elements a workgroup stages at a time, the longest chain summed in the compute type, the largest
+    grid, and the tiles a workgroup walks before it flushes its chains to f64. A measurement entry point
+    (libfedagg_probe.so, the same source as the product library): tools and tests place sizes with it."""
+    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _abi.check(_abi.load_probe().fa_pairwise_sqdist_geometry(fa_dtype(dtype), int(K), ctypes.byref(te),
+                                                             ctypes.byref(r), ctypes.byref(wg), ctypes.byref(ft)))
+    return te.value, r.value, wg.value, ft.value
+
+
+def sqdist_rtol(dtype, P):
+    """Relative error bound of every entry of :func:`pairwise_sqdist` against exact arithmetic on the
+    converted values: ``(R + 4) * 2**-24`` for float32 / float16 / bfloat16 updates (chains of at most R
+    terms in f32, summed in f64), ``(P + 4) * 2**-53`` for float64 / int32 / int64 ones.
+    R is the library's compile-time constant ``FA_PAIR_CHAIN_TERMS`` (include/fedagg.h)."""
+    dt = dtype if isinstance(dtype, torch.dtype) else torch_dtype(dtype)
+    if dt in _SQDIST_F32:
+        return (_abi.PAIR_CHAIN_TERMS + 4) * 2.0 ** -24
+    if dt in _SQDIST_F64:
+        return (int(P) + 4) * 2.0 ** -53
+    raise TypeError(f"pairwise_sqdist: dtype {dt} is not supported")
+
+
+def pairwise_sqdist(updates, out=None, accumulate=False, stream=None):
+    """Squared Euclidean distances between K updates on device (``fa_pairwise_sqdist``): a K x K
+    float64 device tensor, exactly symmetric with a zero diagonal, every entry within
+    :func:`sqdist_rtol` of the exact sum, the same bits on every call.
+
+    updates     1 <= K <= 64 flat device tensors of one dtype (float32 / float64 / float16 / bfloat16 /
+                int32 / int64) and one length
+    out         K x K float64 device tensor (contiguous); allocated when None
+    accumulate  add this call's distances to ``out`` instead of writing it (dtype groups, slices)
+    """
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"pairwise_sqdist takes 1..{MAX_ORDER_K} updates, got {K}")
+    if not isinstance(updates[0], torch.Tensor):
+        raise TypeError("updates[0] must be a torch.Tensor")
+    P = updates[0].numel()
+    dev = updates[0].device
+    upd_dt = updates[0].dtype
+    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
+        raise TypeError(f"pairwise_sqdist: dtype {upd_dt} is not supported")
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one pairwise_sqdist call must share a dtype")
+    if out is None:
+        if accumulate:
+            raise ValueError("pairwise_sqdist: accumulate needs the matrix to add to (out)")
+    else:
+        _check_dev("out", out, K * K, dev)
+        if out.dtype != torch.float64:
+            raise TypeError(f"pairwise_sqdist: out must be float64, got {out.dtype}")
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):               # scratch (and a fresh D) belong to the launching stream
+            if out is None:
+                out = torch.empty((K, K), dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, int(lib.fa_pairwise_sqdist_work(K, P))), dtype=torch.float64, device=dev)
+        rc = lib.fa_pairwise_sqdist(out.data_ptr(), _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt),
+                                    K, P, int(bool(accumulate)), work.data_ptr(), ctypes_stream(s))
+    _abi.check(rc)
+    return out
+
+
 def running_mean(g, m, a, b, T, stream=None):
     """``g = (g*a + m*b)/T`` in place (``fa_running_mean``): one step of the reference's
     incremental server-function example (sf_incremental_aggregation.py:36-37)."""

@@ -1,4 +1,5 @@
-"""Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median.
+"""Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median, and the
+selection rules Krum / Multi-Krum.
 
 Unlike the FedAvg fold, which sees one client at a time, an order statistic needs all K updates of a
 round at once: per element, the K values are sorted, the ``trim`` smallest and largest dropped and the
@@ -13,7 +14,13 @@ round's updates — in HBM while ``budget.HbmBudget`` admits them, on the host o
     ``base + lo``; each slice's result is copied out before its buffer is reused. HBM use is bounded
     by the budget plus the ring: never an OOM, never a dropped client.
 
-Both rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
+Krum / Multi-Krum (Blanchard et al., 2017) select WHOLE updates instead of filtering
+each coordinate: ``select_mean(f, m)`` makes one pass over the held updates for the K x K matrix of
+squared distances (``fa_pairwise_sqdist``, kernel ``k_pair_sqdist``; dtype groups and slices are summed
+into one matrix on the device), selects on the host (:func:`krum_select`) and takes the plain mean of
+the selected updates with the reduction above at ``trim = 0``.
+
+All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
 ``ops.MAX_ORDER_K`` (64) updates per round.
 
 Stream ordering (the rules DESIGN.md records for fresh HBM, §3.7): a buffer is allocated on the
@@ -51,6 +58,52 @@ def trim_count(trim_fraction, K):
     return max(0, min(math.floor(trim_fraction * K), (K - 1) // 2))
 
 
+def krum_f(byzantine_fraction, K):
+    """Byzantine clients Krum assumes among K: ``floor(byzantine_fraction * K)``, never more than the
+    paper's condition ``2f + 2 < K`` allows (``(K - 3) // 2``); 0 below K = 3."""
+    import math
+    if K < 3:
+        return 0
+    return max(0, min(math.floor(byzantine_fraction * K), (K - 3) // 2))
+
+
+def krum_scores(D, f):
+    """Krum's score of each of the K clients of the K x K squared-distance matrix ``D``, in float64:
+    the sum of the ``nn = max(K - f - 2, min(1, K - 1))`` smallest ``D[i][j]``, j != i, sorted ascending
+    and summed in that order. A non-finite entry counts as +inf."""
+    D = np.array(D, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError(f"a square distance matrix is needed, got shape {D.shape}")
+    K = D.shape[0]
+    if not 0 <= f < max(K, 1):
+        raise ValueError(f"f={f} of K={K} clients")
+    D[~np.isfinite(D)] = np.inf
+    nn = max(K - f - 2, min(1, K - 1))
+    scores = np.zeros(K, dtype=np.float64)
+    for i in range(K):
+        near = np.sort(np.delete(D[i], i))[:nn]
+        acc = np.float64(0.0)
+        for v in near:
+            acc = acc + v
+        scores[i] = acc
+    return scores
+
+
+def krum_select(D, f, m):
+    """The FIFO indices (ascending) of the ``m`` clients with the smallest :func:`krum_scores`; ties go
+    to the lower index. Krum is ``m = 1``, Multi-Krum ``m = K - f``. Raises ``ValueError`` when fewer
+    than ``m`` scores are finite: there is nothing trustworthy to select."""
+    scores = krum_scores(D, f)
+    K = scores.size
+    if not 1 <= m <= K:
+        raise ValueError(f"m={m} of K={K} clients")
+    finite = int(np.isfinite(scores).sum())
+    if finite < m:
+        raise ValueError(f"only {finite} of {K} Krum scores are finite, {m} are to be selected")
+    order = np.argsort(scores, kind="stable")          # stable: equal scores stay in FIFO order
+    return sorted(int(i) for i in order[:m])
+
+
 def _several_devices():
     from .aggregators.fedavg import env_devices
     devs = env_devices()
@@ -80,6 +133,7 @@ class RobustPipeline:
         self.tags = []
         self.host_side = 0           # updates the budget (or a full HBM) left on the host
         self._h2d, self._kern = [], []
+        self.selected, self.scores = None, None     # select_mean: FIFO indices, float64 scores
         self.time_pack = 0.0
         self.time_d2h = 0.0
         self.add(first, tag)
@@ -151,19 +205,104 @@ class RobustPipeline:
             self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
         return out
 
+    def select_mean(self, f, m):
+        """Krum (``m = 1``) / Multi-Krum (``m = K - f``): the unweighted mean of the ``m`` updates that
+        :func:`krum_select` picks, as host arrays like :meth:`result`'s; ``self.selected`` (FIFO indices)
+        and ``self.scores`` stay on the pipeline.
+
+        Pass 1 walks the dtype groups — slice by slice where updates sit on the host, through the same
+        ring as :meth:`result` — and sums their squared distances into one K x K matrix on the device
+        (``ops.pairwise_sqdist(..., accumulate=...)``); the matrix goes to the host and the selection is
+        made there in float64. Pass 2 is the trimmed mean at ``trim = 0`` over the selected updates only
+        (``A(y) / 1``, the converting copy, for Krum's single one). A selected update that sits on the
+        host is therefore uploaded a second time, slice by slice: HBM stays bounded by the budget plus
+        the ring. Raises ``ValueError`` when fewer than ``m`` clients have a finite score."""
+        K = len(self.updates)
+        if not 1 <= K <= ops.MAX_ORDER_K:
+            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        if not (0 <= f < K and 1 <= m <= K):
+            raise ValueError(f"f={f}, m={m} of {K} updates")
+        out = [None] * len(self.layout.shapes)
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
+                for u in self.updates:
+                    if isinstance(u, StagedModel):
+                        self.compute.wait_event(u.ready)
+                D = torch.zeros((K, K), dtype=torch.float64, device=self.device)
+                written = False
+                for dt in self.layout.groups:
+                    written = self._distance_group(dt, D, written)
+                tic = time.perf_counter()
+                Dh = D.cpu().numpy()                 # (synchronises the compute stream)
+                self.time_d2h += time.perf_counter() - tic
+                self.scores = krum_scores(Dh, f)
+                self.selected = krum_select(Dh, f, m)
+                hosts = {dt: self._reduce_group(dt, 0, self.selected) for dt in self.layout.groups}
+                tic = time.perf_counter()
+                self.compute.synchronize()
+                self.time_d2h += time.perf_counter() - tic
+        except BaseException:
+            torch.cuda.synchronize(self.device)
+            raise
+        for dt in self.layout.groups:
+            self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
+        return out
+
     def _host_flat(self, arrays, dt):
         """(flat array, element offset in the group) of the non-empty members of group ``dt``."""
         return [(np.ascontiguousarray(arrays[i]).reshape(-1), off) for i, off in self.layout.members[dt]
                 if self.layout.sizes[i]]
 
-    def _reduce_group(self, dt, trim):
+    def _reduce_group(self, dt, trim, subset=None):
+        """Group ``dt`` of the trimmed mean over the held updates — all of them, or those at the FIFO
+        indices ``subset`` — as a pinned host tensor."""
         n = self.layout.group_elems[dt]
-        tdt, odt = ops.torch_dtype(dt), self._out_dt[dt]
+        odt = self._out_dt[dt]
         host = torch.empty(n, dtype=odt, pin_memory=True)
         if n == 0:                                   # only empty tensors: no launch
             return host
+        outs = {}
+
+        def launch(b, lo, hi, views, step):
+            if b not in outs:
+                outs[b] = torch.empty(step, dtype=odt, device=self.device)
+            ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
+
+        def after(b, lo, hi):
+            # the result leaves on the compute stream: in order behind its launch and ahead of the
+            # launch that reuses outs[b]
+            host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
+
+        self._walk_group(dt, subset, launch, after)
+        return host
+
+    def _distance_group(self, dt, D, written):
+        """Add group ``dt``'s squared distances to ``D`` (written, not added to, by the first launch of
+        the round); returns whether ``D`` has been written."""
+        if self.layout.group_elems[dt] == 0:
+            return written
+        state = [written]
+
+        def launch(b, lo, hi, views, step):
+            ops.pairwise_sqdist(views, out=D, accumulate=state[0], stream=self.compute)
+            state[0] = True
+
+        self._walk_group(dt, None, launch, None)
+        return state[0]
+
+    def _walk_group(self, dt, subset, launch, after):
+        """Run ``launch(b, lo, hi, views, step)`` over group ``dt`` of the updates at ``subset`` (all when
+        None): once when they all sit in HBM, else slice by slice with the host-side ones copied through
+        the two-buffer ring; ``after(b, lo, hi)`` follows each launch's timing events.
+
+        Every view handed to ``launch`` starts on a 16-byte boundary, so the kernels take their 16-byte
+        load paths: a staged update's group starts at a multiple of ``layout.ALIGN`` bytes, slices
+        start at multiples of ``SLICE_ALIGN`` elements, and the ring's rows are padded to one."""
+        n = self.layout.group_elems[dt]
+        tdt = ops.torch_dtype(dt)
         isz, goff = dt.itemsize, self.layout.group_byte_offset[dt]
-        on_host = [k for k, u in enumerate(self.updates) if not isinstance(u, StagedModel)]
+        used = list(range(len(self.updates))) if subset is None else list(subset)
+        on_host = [k for k in used if not isinstance(self.updates[k], StagedModel)]
         if on_host:
             step = max(SLICE_ALIGN, SLICE_BYTES // isz // SLICE_ALIGN * SLICE_ALIGN)
         else:
@@ -174,8 +313,8 @@ class RobustPipeline:
         ring = None
         if on_host:
             with torch.cuda.stream(self.copy):       # allocated on the stream that writes it
-                ring = reuse.watch(torch.empty((nbuf, len(on_host), step), dtype=tdt, device=self.device), self.copy)
-        outs = [torch.empty(step, dtype=odt, device=self.device) for _ in range(nbuf)]
+                row = -(-step // SLICE_ALIGN) * SLICE_ALIGN        # (a group shorter than a slice: step = n)
+                ring = reuse.watch(torch.empty((nbuf, len(on_host), row), dtype=tdt, device=self.device), self.copy)
         consumed = [None] * nbuf
         for s, lo in enumerate(range(0, n, step)):
             hi, b = min(n, lo + step), s % nbuf
@@ -195,7 +334,8 @@ class RobustPipeline:
                 self._h2d.append((h0, h1))
                 self.compute.wait_event(h1)
             views, r = [], 0
-            for u in self.updates:
+            for k in used:
+                u = self.updates[k]
                 if isinstance(u, StagedModel):
                     views.append(u.dev[goff + lo * isz:goff + hi * isz].view(tdt))
                 else:
@@ -203,18 +343,16 @@ class RobustPipeline:
                     r += 1
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             k0.record(self.compute)
-            ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
+            launch(b, lo, hi, views, step)
             k1.record(self.compute)
             self._kern.append((k0, k1))
             if on_host:
                 consumed[b] = torch.cuda.Event()
                 consumed[b].record(self.compute)
-            # the result leaves on the compute stream: in order behind its launch and ahead of the
-            # launch that reuses outs[b]
-            host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
+            if after is not None:
+                after(b, lo, hi)
         if ring is not None:
             ring.record_stream(self.compute)
-        return host
 
     # ---- bookkeeping -----------------------------------------------------------------
     def timings(self):

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 9
+#define FA_ABI_VERSION 10
 
 /* element type codes */
 enum fa_dtype {
@@ -364,6 +364,38 @@ int fa_host_device_ptr(const void* host, void** dptr);
  */
 int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype,
                     int K, int trim, int64_t P, void* stream);
+
+/*
+ * fa_pairwise_sqdist (ABI 10): the K x K matrix of squared Euclidean distances between K client updates,
+ * the input of Krum / Multi-Krum (Blanchard et al., 2017) and of any rule that selects whole updates.
+ * With C the compute type of upd_dtype — f32 for F32 / F16 / BF16 (each value widened exactly), f64 for
+ * F64 / I32 / I64 (each value converted with one rounding) —
+ *     D[i][j] = sum_p (C(u_i[p]) - C(u_j[p]))^2      for i != j,      D[i][i] = 0 exactly.
+ * Each difference is rounded once in C; the squares are summed in C (fused multiply-add) in chains of at
+ * most R = FA_PAIR_CHAIN_TERMS terms (a compile-time constant of the library); the chain totals
+ * are summed in f64. Every term is non-negative, so against exact arithmetic on the converted values the
+ * relative error of an entry is at most (R + 4) * 2^-24 for C = f32 and (P + 4) * 2^-53 for C = f64.
+ * D is exactly symmetric: the upper triangle is computed and mirrored. A non-finite input value makes the
+ * entries of its client inf or NaN; that is not an error.
+ *
+ * Deterministic: the partition of the elements into chains and partial sums depends only on (K, P,
+ * upd_dtype), the partials are combined in a fixed order and there is no floating-point atomic — the
+ * same inputs give the same bits on every call, whether or not the client pointers are 16-byte aligned.
+ *
+ * D        DEVICE buffer of K x K doubles, row-major
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * accumulate  0: D is written; 1: the call's distances are added to D in f64 (D[i][j] += d, D[j][i] += d)
+ *          — a model's dtype groups or slices summed into one D without a host round trip
+ * work     DEVICE scratch of fa_pairwise_sqdist_work(K, P) doubles (>= 1; enough for every dtype)
+ * FA_EINVAL: a null pointer (an entry of updates included, when P > 0), K outside 1..64, P < 0; FA_EDTYPE: a dtype
+ * outside the six above — all before any HIP call. P = 0 and K = 1 are FA_OK: with accumulate = 0 the
+ * zeros (the single 0) are still written by a launch; with accumulate = 1 there is nothing to add and
+ * nothing is launched. fa_last_kernel reports "k_pair_sqdist".
+ */
+#define FA_PAIR_CHAIN_TERMS 1024 /* R: the longest chain summed in the compute type */
+int64_t fa_pairwise_sqdist_work(int K, int64_t P);
+int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int K, int64_t P, int accumulate,
+                       double* work, void* stream);
 
 #ifdef __cplusplus
 }

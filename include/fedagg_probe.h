@@ -28,6 +28,13 @@ int fa_stream_copy(void* dst, const void* src, int64_t bytes, void* stream);
 /* out[i] = sum_k bufs[k][i] (fp32, K <= 64) with exactly the traversal of the FedAvg fold
  * kernel but one add per element: the access-pattern ceiling of fa_fedavg_fold.        */
 int fa_stream_sum(float* out, const float* const* bufs, int K, int64_t P, void* stream);
+/* The launch geometry of fa_pairwise_sqdist for (upd_dtype, K): the tile length TE (elements a
+ * workgroup stages at a time), R (= FA_PAIR_CHAIN_TERMS), the largest grid, and the tiles a workgroup
+ * walks between two flushes of its chains — what tools and tests need to put sizes on the kernel's
+ * edges; none of it is part of the product ABI. Any output pointer may be NULL. FA_EINVAL for K
+ * outside 1..64, FA_EDTYPE for a dtype outside the six of fa_pairwise_sqdist.                  */
+int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                                int* flush_tiles);
 
 /* The knobs of fa_tune (process-global; measurement and tuning only). Every setting computes the
  * reference's bits except OPT_MIX and OPT_WIN_PERIOD > 0 without OPT_WIN_PROD, which run access-
