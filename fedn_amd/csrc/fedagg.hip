@@ -1571,13 +1571,23 @@ k_fedopt(const OptBuffers b, const OptScalars s, const ClientTable<typename PG::
 template <typename T> __device__ __forceinline__ T as_t(double v) { return (T)v; }
 
 // numpyhelper.add / subtract on float16 arrays: x*a + y*b with the python scalars cast to half and
-// every op computed in float and rounded to half (numpy's half loops)
+// every op rounded to half (numpy's half loops compute in float and round: the float product of two
+// halves is exact and the float sum is wide enough, 24 >= 2*11+2, so each is the IEEE half op). Written
+// in half arithmetic on purpose: for rh(float(x) * ah) the compiler emitted a mixed-precision fma with a
+// +0 addend, which turns a product of -0 into +0, and (-0)*a + (-0)*b came out +0.
+__device__ __forceinline__ _Float16 f16_value(f16 v) {
+    _Float16 h;
+    __builtin_memcpy(&h, &v.bits, 2);
+    return h;
+}
 __global__ void __launch_bounds__(kBlock) k_axpby_half(f16* __restrict__ out, const f16* __restrict__ x,
                                                        const f16* __restrict__ y, float ah, float bh, int64_t P) {
+    const _Float16 a = (_Float16)ah, b = (_Float16)bh;          // halves already (to_half_value): exact
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < P; i += (int64_t)gridDim.x * kBlock) {
-        const float xa = CF16::rh(f16_to_f32(x[i].bits) * ah);
-        const float yb = CF16::rh(f16_to_f32(y[i].bits) * bh);
-        out[i] = f16{f32_to_f16(xa + yb)};
+        const _Float16 xa = f16_value(x[i]) * a;
+        const _Float16 yb = f16_value(y[i]) * b;
+        const _Float16 r = xa + yb;
+        __builtin_memcpy(&out[i].bits, &r, 2);
     }
 }
 
@@ -2772,6 +2782,8 @@ int fa_elementwise(int op, void* out, int out_dtype, const void* x, int x_dtype,
                      : (op == FA_EW_AXPBY || ((op == FA_EW_MUL || op == FA_EW_DIV) && y)) ? fa_promote(x_dtype, y_dtype)
                      : x_dtype;
     if (out_dtype != want) return fail(FA_EDTYPE, "fa_elementwise: output dtype must be %d", want);
+    // np.power(x32, a): the python float is a weak scalar, so numpy raises to float32(a)
+    if (op == FA_EW_POW && x_dtype == FA_F32) a = (double)(float)a;
     const dim3 grid((unsigned)std::min<int64_t>((P + kBlock - 1) / kBlock, 8192));
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define FA_EW(TX, TY, TO) \

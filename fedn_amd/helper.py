@@ -266,9 +266,11 @@ class Helper:
         """np.power(x, a) per tensor (numpyhelper.py:94-104), numpy's dtype rules: a float array
         keeps its dtype for a python scalar a; an integer array with a non-negative python int
         stays integer (exponentiation by squaring, wrapping), with a float a becomes float64.
-        a == 2 is x*x, numpy's exact result; other float exponents run the device pow (numpy's
-        own float power comes from its host SIMD library and differs between hosts: parity is
-        1e-6 relative for float32, 1e-15 for float64)."""
+        a == 2 is x*x, numpy's exact result; other float exponents run the device pow. The exponent
+        is a weak scalar, as in numpy: a float32 array is raised to float32(a) (fa_elementwise rounds
+        it), a float16 one to float16(a), a float64 one to a itself (numpy's own float power comes
+        from its host SIMD library and differs between hosts: parity is 1e-6 relative for float32,
+        1e-15 for float64)."""
         import torch
 
         from . import ops

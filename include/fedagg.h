@@ -217,10 +217,14 @@ int fa_running_mean(void* g, int dtype, const void* m, double a, double b, doubl
  *   FA_EW_SQUARE  out = x*x                        numpyhelper.power(m, 2)
  *   FA_EW_SIGN    out = sign(x) (+-1, 0, NaN)      numpyhelper.sign
  *   FA_EW_FILL    out = 1.0*a (x unused)           numpyhelper.ones
- *   FA_EW_POW     out = x**a (float a)             numpyhelper.power(m, a); f32 computed as the f64
- *                                                  power rounded once (numpy's own float power is its
- *                                                  host libm's / SIMD library's: not bit-reproducible
- *                                                  across hosts; parity: 1e-6 relative, f64 1e-15)
+ *   FA_EW_POW     out = x**a (float a)             numpyhelper.power(m, a) = np.power(x, a). a is a weak
+ *                                                  scalar: an f32 x is raised to (float)a, as numpy
+ *                                                  does, computed as RN_f32(pow((double)x, (float)a))
+ *                                                  with the f64 pow; an f64 x to a itself. C99 Annex F
+ *                                                  special cases, bit for bit. (numpy's own float power
+ *                                                  is its host libm's / SIMD library's: not
+ *                                                  bit-reproducible across hosts; parity: 1e-6
+ *                                                  relative, f64 1e-15)
  *   FA_EW_IPOW    out = x**a, x any integer dtype (I8..I64, U8..U64), a a non-negative integer:
  *                 exponentiation by squaring with wrapping products, out_dtype = x_dtype (numpy's
  *                 integer power)
@@ -233,6 +237,8 @@ int fa_running_mean(void* g, int dtype, const void* m, double a, double b, doubl
  *                 |a| < 2^53; numpy refuses an a outside T's range, and so must the caller) —
  *                 difference and product wrap in T, then the float64 divide by b and add
  * out_dtype must be the numpy result dtype of the op.
+ * out may be exactly x or exactly y when it has that operand's dtype (each element is read before
+ * it is written, by the same lane: `acc /= total`, `x = x*a + y*b`); a partial overlap is not allowed.
  */
 enum fa_ew_op { FA_EW_AXPBY = 0, FA_EW_MUL = 1, FA_EW_DIV = 2, FA_EW_SQRT = 3, FA_EW_SQUARE = 4, FA_EW_SIGN = 5,
                 FA_EW_FILL = 6, FA_EW_POW = 7, FA_EW_IPOW = 8, FA_EW_IFOLD = 9,
