@@ -116,6 +116,12 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,    # D, updates, upd_dtype
         ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
         ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
+    "fa_wmean_sqdist_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),      # K, P
+    "fa_weighted_mean_sqdist": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,                    # out (or NULL), out_dtype, dist
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double),   # updates, upd_dtype, beta
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
+        ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -129,9 +135,13 @@ PROBE_EXPORTS = {
         ctypes.c_int, ctypes.c_int,                                        # upd_dtype, K
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, R, grid, tiles per flush
+    "fa_wmean_sqdist_geometry": (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_int,                                        # upd_dtype, K
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

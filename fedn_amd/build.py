@@ -9,6 +9,7 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "fedagg.hip")
 ORDER_SRC = os.path.join(HERE, "csrc", "order_mean.h")   # k_order_mean (fa_trimmed_mean), included by SRC
 PAIR_SRC = os.path.join(HERE, "csrc", "pair_dist.h")     # k_pair_sqdist (fa_pairwise_sqdist), included by SRC
+WMEAN_SRC = os.path.join(HERE, "csrc", "wmean_dist.h")   # k_wmean_dist (fa_weighted_mean_sqdist), included by SRC
 HDR = os.path.join(ROOT, "include", "fedagg.h")
 OUT = os.path.join(HERE, "libfedagg.so")
 PROBE_HDR = os.path.join(ROOT, "include", "fedagg_probe.h")
@@ -92,7 +93,7 @@ def build(force=False, verbose=True):
 
 def build_hip(force=False, verbose=True, probe=False):
     out = PROBE_OUT if probe else OUT
-    deps = (SRC, ORDER_SRC, PAIR_SRC, HDR, PROBE_HDR)
+    deps = (SRC, ORDER_SRC, PAIR_SRC, WMEAN_SRC, HDR, PROBE_HDR)
     if not force and not _stale(out, *deps):
         return out
     tmp = out + ".tmp"

@@ -2445,6 +2445,9 @@ int launch_fedopt(const OptBuffers& b, const OptScalars& s, const void* const* u
 // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "pair_dist.h"
 
+// weighted mean and the K squared distances to it, one pass (k_wmean_dist, fa_weighted_mean_sqdist)
+#include "wmean_dist.h"
+
 }  // namespace
 
 // ============================================================================
@@ -3176,6 +3179,66 @@ int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int
     if (accumulate && (P == 0 || K == 1)) return FA_OK;      // nothing to add: no launch
     if (f32fam) return launch_pair_sqdist<float>(D, updates, upd_dtype, K, P, accumulate, work, st);
     return launch_pair_sqdist<double>(D, updates, upd_dtype, K, P, accumulate, work, st);
+}
+
+#ifdef FEDAGG_PROBES
+int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                             int* flush_tiles) {
+    g_err[0] = 0;
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_wmean_sqdist_geometry: K=%d outside 1..%d", K, kMaxK);
+    if (upd_dtype != FA_F32 && upd_dtype != FA_F16 && upd_dtype != FA_BF16 && !pair_family64(upd_dtype))
+        return fail(FA_EDTYPE, "fa_wmean_sqdist_geometry: unsupported dtype %d", upd_dtype);
+    const WmGeom gm = wm_geom_dt(upd_dtype, K);
+    if (tile_elems) *tile_elems = gm.TE;
+    if (chain_terms) *chain_terms = kWmChain;
+    if (max_workgroups) *max_workgroups = gm.GRID;
+    if (flush_tiles) *flush_tiles = gm.FT;
+    return FA_OK;
+}
+#endif  // FEDAGG_PROBES
+
+int64_t fa_wmean_sqdist_work(int K, int64_t P) {
+    if (K < 1 || K > kMaxK || P < 0) return 0;
+    // f64 updates: the smallest tile and the largest grid, so the most workgroups; kMaxK doubles per workgroup
+    return std::max<int64_t>(wm_workgroups(P, wm_geom_dt(FA_F64, K)) * kMaxK, 1);
+}
+
+int fa_weighted_mean_sqdist(void* out, int out_dtype, double* dist, const void* const* updates, int upd_dtype,
+                            const double* beta, int K, int64_t P, int accumulate, double* work, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!dist || !beta || !updates || !work) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: null pointer argument");
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: K=%d outside 1..%d", K, kMaxK);
+    if (P < 0) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: negative size (P=%lld)", (long long)P);
+    const bool f32fam = upd_dtype == FA_F32 || upd_dtype == FA_F16 || upd_dtype == FA_BF16;
+    if (!f32fam && !pair_family64(upd_dtype))
+        return fail(FA_EDTYPE, "fa_weighted_mean_sqdist: unsupported dtype %d", upd_dtype);
+    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
+    if (out_dtype != want)
+        return fail(FA_EDTYPE, "fa_weighted_mean_sqdist: updates of dtype %d give a mean of dtype %d, not %d", upd_dtype,
+                    want, out_dtype);
+    double bc[kMaxK];
+    int kfirst = -1;
+    for (int k = 0; k < K; ++k) {
+        if (!(beta[k] >= 0.0) || std::isinf(beta[k]))
+            return fail(FA_EINVAL, "fa_weighted_mean_sqdist: beta[%d]=%g is negative or not finite", k, beta[k]);
+        bc[k] = f32fam ? (double)(float)beta[k] : beta[k];       // C(beta[k]), cast once
+        if (std::isinf(bc[k]))
+            return fail(FA_EINVAL, "fa_weighted_mean_sqdist: beta[%d]=%g is not finite in the compute type", k, beta[k]);
+        if (bc[k] != 0.0 && kfirst < 0) kfirst = k;
+    }
+    if (kfirst < 0) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: every weight is zero in the compute type");
+    for (int k = 0; k < K && P > 0; ++k)                     // (an empty buffer may be a null pointer)
+        if (!updates[k]) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: updates[%d] is NULL", k);
+    if (accumulate && P == 0) return FA_OK;                  // nothing to add: no launch
+    switch (upd_dtype) {
+        case FA_F32: return launch_wmean_dist<float>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+        case FA_F16: return launch_wmean_dist<f16>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+        case FA_BF16: return launch_wmean_dist<bf16>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+        case FA_F64: return launch_wmean_dist<double>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+        case FA_I32: return launch_wmean_dist<int32_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+        default: return launch_wmean_dist<int64_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+    }
 }
 
 #ifdef FEDAGG_PROBES

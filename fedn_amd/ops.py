@@ -313,6 +313,80 @@ def pairwise_sqdist(updates, out=None, accumulate=False, stream=None):
     return out
 
 
+def wmean_geometry(dtype, K):
+    """``(TE, chain, max workgroups, tiles per flush)`` of ``fa_weighted_mean_sqdist`` for K updates of
+    ``dtype``: the elements a workgroup stages at a time, the longest chain its kernel sums in the
+    compute type (at most R of :func:`sqdist_rtol`), the largest grid, and the tiles a workgroup walks
+    between two flushes of its chains to f64. A measurement entry point (libfedagg_probe.so) like
+    :func:`sqdist_geometry`."""
+    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _abi.check(_abi.load_probe().fa_wmean_sqdist_geometry(fa_dtype(dtype), int(K), ctypes.byref(te), ctypes.byref(r),
+                                                          ctypes.byref(wg), ctypes.byref(ft)))
+    return te.value, r.value, wg.value, ft.value
+
+
+def weighted_mean_sqdist(updates, beta, out=None, dist=None, accumulate=False, store=True, stream=None):
+    """One smoothed Weiszfeld step on device (``fa_weighted_mean_sqdist``): the weighted mean
+    ``z = sum_k beta[k] * u_k`` of K updates — summed in index order in the compute type over the clients
+    with a nonzero weight, rounded once to :func:`order_mean_dtype` of the updates' dtype — and the K
+    squared distances ``sum_p (u_k[p] - z[p])**2`` of EVERY update to it, each within
+    :func:`sqdist_rtol` of the exact sum, in one pass that reads every update once. Returns
+    ``(out or None, dist)``; the same bits on every call.
+
+    updates     1 <= K <= 64 flat device tensors of one dtype (float32 / float64 / float16 / bfloat16 /
+                int32 / int64) and one length
+    beta        K weights, finite and >= 0, not all zero (they need not sum to 1)
+    out         flat device tensor for z; allocated when None and ``store``
+    dist        K float64 device values; allocated when None
+    accumulate  add this call's distances to ``dist`` instead of writing it (dtype groups, slices)
+    store       False: z is formed for the distances but not stored (``out`` is left alone; None is returned)
+    """
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"weighted_mean_sqdist takes 1..{MAX_ORDER_K} updates, got {K}")
+    if not isinstance(updates[0], torch.Tensor):
+        raise TypeError("updates[0] must be a torch.Tensor")
+    P = updates[0].numel()
+    dev = updates[0].device
+    upd_dt = updates[0].dtype
+    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
+        raise TypeError(f"weighted_mean_sqdist: dtype {upd_dt} is not supported")
+    out_dt = order_mean_dtype(upd_dt)
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one weighted_mean_sqdist call must share a dtype")
+    beta = [float(b) for b in beta]
+    if len(beta) != K:
+        raise ValueError(f"weighted_mean_sqdist: {len(beta)} weights for {K} updates")
+    if out is not None:
+        _check_dev("out", out, P, dev)
+        if out.dtype != out_dt:
+            raise TypeError(f"weighted_mean_sqdist: out must be {out_dt} for {upd_dt} updates, got {out.dtype}")
+    if dist is None:
+        if accumulate:
+            raise ValueError("weighted_mean_sqdist: accumulate needs the distances to add to (dist)")
+    else:
+        _check_dev("dist", dist, K, dev)
+        if dist.dtype != torch.float64:
+            raise TypeError(f"weighted_mean_sqdist: dist must be float64, got {dist.dtype}")
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):               # scratch and fresh outputs belong to the launching stream
+            if out is None and store:
+                out = torch.empty(P, dtype=out_dt, device=dev)
+            if dist is None:
+                dist = torch.empty(K, dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, int(lib.fa_wmean_sqdist_work(K, P))), dtype=torch.float64, device=dev)
+        rc = lib.fa_weighted_mean_sqdist(out.data_ptr() if store else None, fa_dtype(out_dt), dist.data_ptr(),
+                                         _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt),
+                                         _abi.double_array(beta), K, P, int(bool(accumulate)), work.data_ptr(),
+                                         ctypes_stream(s))
+    _abi.check(rc)
+    return (out if store else None), dist
+
+
 def running_mean(g, m, a, b, T, stream=None):
     """``g = (g*a + m*b)/T`` in place (``fa_running_mean``): one step of the reference's
     incremental server-function example (sf_incremental_aggregation.py:36-37)."""

@@ -1,5 +1,5 @@
-"""Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median, and the
-selection rules Krum / Multi-Krum.
+"""Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median, the
+selection rules Krum / Multi-Krum, and the geometric median.
 
 Unlike the FedAvg fold, which sees one client at a time, an order statistic needs all K updates of a
 round at once: per element, the K values are sorted, the ``trim`` smallest and largest dropped and the
@@ -19,6 +19,12 @@ each coordinate: ``select_mean(f, m)`` makes one pass over the held updates for 
 squared distances (``fa_pairwise_sqdist``, kernel ``k_pair_sqdist``; dtype groups and slices are summed
 into one matrix on the device), selects on the host (:func:`krum_select`) and takes the plain mean of
 the selected updates with the reduction above at ``trim = 0``.
+
+The geometric median (RFA: Pillutla, Kakade and Harchaoui) is the point with the
+smallest sum of distances to the updates: ``geometric_median(iterations, nu)`` runs smoothed Weiszfeld
+steps, each ONE pass over the held updates that forms the weighted mean and the K distances to it
+(``fa_weighted_mean_sqdist``, kernel ``k_wmean_dist``); the weights of the next step come from the
+distances on the host (:func:`weiszfeld_weights`).
 
 All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
 ``ops.MAX_ORDER_K`` (64) updates per round.
@@ -104,6 +110,25 @@ def krum_select(D, f, m):
     return sorted(int(i) for i in order[:m])
 
 
+def weiszfeld_weights(d, nu):
+    """The weights of one smoothed Weiszfeld step from the K squared distances ``d`` to the current
+    point, in float64: ``w_k = 1 / max(nu, sqrt(d_k))`` where ``d_k`` is finite, else 0; the sum is taken
+    in index order and ``beta = w / sum``. Raises ``ValueError`` when every weight is 0."""
+    d = np.asarray(d, dtype=np.float64).reshape(-1)
+    nu = np.float64(nu)
+    w = np.zeros(d.size, dtype=np.float64)
+    total = np.float64(0.0)
+    with np.errstate(invalid="ignore"):
+        for k in range(d.size):
+            if np.isfinite(d[k]):
+                r = np.sqrt(d[k])
+                w[k] = np.float64(1.0) / (nu if nu > r else r)       # (a NaN r, from d < 0, keeps nu)
+            total = total + w[k]
+    if not total > 0.0:
+        raise ValueError(f"no client has a finite distance: {d}")
+    return w / total
+
+
 def _several_devices():
     from .aggregators.fedavg import env_devices
     devs = env_devices()
@@ -134,6 +159,8 @@ class RobustPipeline:
         self.host_side = 0           # updates the budget (or a full HBM) left on the host
         self._h2d, self._kern = [], []
         self.selected, self.scores = None, None     # select_mean: FIFO indices, float64 scores
+        self.weights, self.distances = None, None   # geometric_median: the last pass's beta, sqrt(d)
+        self.excluded, self.trace = [], []          # ... clients shut out as non-finite; (beta, d) per pass
         self.time_pack = 0.0
         self.time_d2h = 0.0
         self.add(first, tag)
@@ -228,13 +255,7 @@ class RobustPipeline:
                 for u in self.updates:
                     if isinstance(u, StagedModel):
                         self.compute.wait_event(u.ready)
-                D = torch.zeros((K, K), dtype=torch.float64, device=self.device)
-                written = False
-                for dt in self.layout.groups:
-                    written = self._distance_group(dt, D, written)
-                tic = time.perf_counter()
-                Dh = D.cpu().numpy()                 # (synchronises the compute stream)
-                self.time_d2h += time.perf_counter() - tic
+                Dh = self._distance_matrix(K)
                 self.scores = krum_scores(Dh, f)
                 self.selected = krum_select(Dh, f, m)
                 hosts = {dt: self._reduce_group(dt, 0, self.selected) for dt in self.layout.groups}
@@ -247,6 +268,124 @@ class RobustPipeline:
         for dt in self.layout.groups:
             self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
         return out
+
+    def _distance_matrix(self, K):
+        """The K x K matrix of squared distances between the held updates, on the host: one pass over
+        the dtype groups, summed into one matrix on the device. Called on the compute stream with the
+        staged updates' ``ready`` events already waited for."""
+        D = torch.zeros((K, K), dtype=torch.float64, device=self.device)
+        written = False
+        for dt in self.layout.groups:
+            written = self._distance_group(dt, D, written)
+        tic = time.perf_counter()
+        Dh = D.cpu().numpy()                         # (synchronises the compute stream)
+        self.time_d2h += time.perf_counter() - tic
+        return Dh
+
+    def geometric_median(self, iterations, nu):
+        """The smoothed geometric median of the held updates (RFA: Pillutla, Kakade and Harchaoui) by
+        ``iterations`` Weiszfeld steps, as host arrays like :meth:`result`'s.
+
+        Pass 0 takes the plain mean (``beta = 1/K``) and the K squared distances to it in ONE fused pass
+        (``ops.weighted_mean_sqdist``, kernel ``k_wmean_dist``): the dtype groups are walked — slice by
+        slice where updates sit on the host, through the same ring as :meth:`result` — and their
+        distances summed into one vector on the device. Passes 1 .. ``iterations`` take
+        ``beta = weiszfeld_weights(d, nu)`` of the pass before. Only the last pass stores its mean and
+        copies it to the host. Host-side updates are uploaded ONCE PER PASS, slice by slice: HBM stays
+        bounded by the budget plus the ring, at ``iterations + 1`` uploads of what the budget refused.
+
+        A non-finite distance after pass 0 means the plain mean was poisoned. Then the K x K distance
+        matrix (``fa_pairwise_sqdist``) names the clients whose distance to EVERY other client is
+        non-finite; they are excluded (weight 0 in every pass) and pass 0 restarts with ``1/K_good`` on
+        the rest. ``ValueError`` when that excludes nobody or everybody, or when a remaining client's
+        distance is still non-finite.
+
+        Kept on the pipeline: ``weights`` (the last pass's beta), ``distances`` (sqrt of the last pass's
+        d), ``excluded`` (FIFO indices) and ``trace`` (one ``(beta, d)`` pair per pass, float64)."""
+        K = len(self.updates)
+        if not 1 <= K <= ops.MAX_ORDER_K:
+            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        if iterations < 0 or not (nu > 0 and np.isfinite(nu)):
+            raise ValueError(f"iterations={iterations}, nu={nu}")
+        T = 0 if K == 1 else int(iterations)
+        self.weights, self.distances, self.excluded, self.trace = None, None, [], []
+        out = [None] * len(self.layout.shapes)
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
+                for u in self.updates:
+                    if isinstance(u, StagedModel):
+                        self.compute.wait_event(u.ready)
+                beta = np.full(K, 1.0 / K, dtype=np.float64)
+                d, hosts = self._weiszfeld_pass(beta, T == 0)
+                if not np.isfinite(d).all():
+                    Dh = self._distance_matrix(K)
+                    off = ~np.eye(K, dtype=bool)
+                    bad = [k for k in range(K) if K > 1 and not np.isfinite(Dh[k][off[k]]).any()]
+                    if not bad or len(bad) == K:
+                        raise ValueError(f"non-finite distances to the mean ({d}) and {len(bad)} of {K} clients "
+                                         "are non-finite against every other: nothing to exclude")
+                    self.trace = []
+                    self.excluded = bad
+                    beta = np.full(K, 1.0 / (K - len(bad)), dtype=np.float64)
+                    beta[bad] = 0.0
+                    d, hosts = self._weiszfeld_pass(beta, T == 0)
+                    good = np.ones(K, dtype=bool)
+                    good[bad] = False
+                    if not np.isfinite(d[good]).all():
+                        raise ValueError(f"non-finite distances remain after excluding clients {bad}: {d}")
+                for t in range(1, T + 1):
+                    beta = weiszfeld_weights(d, nu)
+                    d, hosts = self._weiszfeld_pass(beta, t == T)
+                tic = time.perf_counter()
+                self.compute.synchronize()
+                self.time_d2h += time.perf_counter() - tic
+        except BaseException:
+            torch.cuda.synchronize(self.device)
+            raise
+        self.weights = beta
+        with np.errstate(invalid="ignore"):
+            self.distances = np.sqrt(d)
+        for dt in self.layout.groups:
+            self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
+        return out
+
+    def _weiszfeld_pass(self, beta, store):
+        """One fused pass over every dtype group with the weights ``beta``: ``(d, hosts)`` — the K
+        squared distances to the weighted mean as a float64 host array, and (``store``) the mean's
+        groups as pinned host tensors, valid once the compute stream is synchronised. Appends
+        ``(beta, d)`` to ``trace``."""
+        K = len(self.updates)
+        beta = np.array(beta, dtype=np.float64)
+        dist = torch.zeros(K, dtype=torch.float64, device=self.device)
+        state = [False]                              # dist is written by the pass's first launch, added to after
+        hosts = {}
+        for dt in self.layout.groups:
+            n = self.layout.group_elems[dt]
+            odt = self._out_dt[dt]
+            host = hosts[dt] = torch.empty(n, dtype=odt, pin_memory=True) if store else None
+            if n == 0:
+                continue
+            outs = {}
+
+            def launch(b, lo, hi, views, step, odt=odt, outs=outs):
+                z = None
+                if store:
+                    if b not in outs:
+                        outs[b] = torch.empty(step, dtype=odt, device=self.device)
+                    z = outs[b][:hi - lo]
+                ops.weighted_mean_sqdist(views, beta, out=z, dist=dist, accumulate=state[0], store=store,
+                                         stream=self.compute)
+                state[0] = True
+
+            def after(b, lo, hi, host=host, outs=outs):
+                host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
+
+            self._walk_group(dt, None, launch, after if store else None)
+        tic = time.perf_counter()
+        d = dist.cpu().numpy()                       # (synchronises the compute stream)
+        self.time_d2h += time.perf_counter() - tic
+        self.trace.append((beta, d))
+        return d, hosts
 
     def _host_flat(self, arrays, dt):
         """(flat array, element offset in the group) of the non-empty members of group ``dt``."""

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 10
+#define FA_ABI_VERSION 11
 
 /* element type codes */
 enum fa_dtype {
@@ -402,6 +402,40 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
 int64_t fa_pairwise_sqdist_work(int K, int64_t P);
 int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int K, int64_t P, int accumulate,
                        double* work, void* stream);
+
+/*
+ * fa_weighted_mean_sqdist (ABI 11): a weighted mean of K client updates and the K squared distances of
+ * the updates to it, in ONE pass over the updates — one smoothed Weiszfeld step of the geometric median
+ * (RFA: Pillutla, Kakade and Harchaoui). With C the compute type of upd_dtype as for fa_pairwise_sqdist
+ * and b_k = C(beta[k]) (each cast once), per element over the clients with b_k != 0 in index order
+ *     acc = b C(u)  for the first,  acc = acc + b C(u)  for the others,      z = acc rounded once to out_dtype,
+ * every product and every add rounded once in C (no FMA, no reassociation). A client with b_k = 0 is no
+ * part of z: its inf or NaN cannot reach it. Then, for EVERY k (b_k = 0 included),
+ *     dist[k] = sum_p (C(u_k[p]) - C(z[p]))^2        with z as stored (or as it would be, out = NULL),
+ * by fa_pairwise_sqdist's arithmetic: the difference rounded once, the squares summed by FMA in chains
+ * of at most FA_PAIR_CHAIN_TERMS terms in C, the chain totals in f64 — relative error at most
+ * (R + 4) * 2^-24 for C = f32 and (P + 4) * 2^-53 for C = f64 against exact arithmetic on C(u), C(z).
+ *
+ * Deterministic as fa_pairwise_sqdist: the partition into tiles, chains and partials depends only on
+ * (K, P, upd_dtype), the grid cap is a constant, partials are combined in a fixed order, there is no
+ * floating-point atomic; the same bits on every call, whether or not the pointers are 16-byte aligned.
+ *
+ * out      DEVICE buffer of P elements of out_dtype, or NULL: z is computed but not stored
+ * out_dtype  F32 for F32 / BF16 updates, F16 for F16, F64 for F64 / I32 / I64
+ * dist     DEVICE buffer of K doubles
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * beta     HOST array of K doubles, each finite and >= 0, not all zero in C
+ * accumulate  0: dist is written; 1: the call's distances are added to it in f64 (dtype groups, slices)
+ * work     DEVICE scratch of fa_wmean_sqdist_work(K, P) doubles (>= 1; enough for every dtype)
+ * FA_EINVAL: a null dist, beta, updates or work, a null entry of updates when P > 0, K outside 1..64,
+ * P < 0, a beta that is negative or not finite, every C(beta) zero; FA_EDTYPE: a dtype outside the six or
+ * an out_dtype that is not the table's — all before any HIP call. P = 0 is FA_OK: with accumulate = 0
+ * the K zeros are still written, with accumulate = 1 nothing is launched. A non-finite input value is not
+ * an error. fa_last_kernel reports "k_wmean_dist".
+ */
+int64_t fa_wmean_sqdist_work(int K, int64_t P);
+int fa_weighted_mean_sqdist(void* out, int out_dtype, double* dist, const void* const* updates, int upd_dtype,
+                            const double* beta, int K, int64_t P, int accumulate, double* work, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,11 @@ int fa_stream_sum(float* out, const float* const* bufs, int K, int64_t P, void* 
  * outside 1..64, FA_EDTYPE for a dtype outside the six of fa_pairwise_sqdist.                  */
 int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
                                 int* flush_tiles);
+/* The same four numbers for fa_weighted_mean_sqdist: the tile length, the longest chain its kernel sums in
+ * the compute type (<= FA_PAIR_CHAIN_TERMS), the largest grid and the tiles between two flushes. Same
+ * status codes.                                                                                      */
+int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                             int* flush_tiles);
 
 /* The knobs of fa_tune (process-global; measurement and tuning only). Every setting computes the
  * reference's bits except OPT_MIX and OPT_WIN_PERIOD > 0 without OPT_WIN_PROD, which run access-
