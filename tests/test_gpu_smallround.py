@@ -4,10 +4,14 @@ model (examples/mnist-pytorch model.py:18-32) and other small float models throu
 another dtype or shape, one too many for the arena, a failed launch — with the admitted updates
 replayed in FIFO order. Also: a model a caller still holds is never overwritten by a later round
 (pooled result blocks are reused only once nothing views them)."""
+import gc
+import weakref
+
 import numpy as np
 import pytest
 import torch
 
+from model_holders import HOLDERS, held_bytes
 from oracle import numpy_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +118,34 @@ def test_a_held_model_is_never_overwritten():
         ptrs.append(model[0].__array_interface__["data"][0])
         del model
     assert len(set(ptrs)) == 1
+    # the model held through something made of it, its list of arrays dropped: more rounds than the
+    # pool has blocks leave its bytes as its round wrote them
+    for kind, hold in HOLDERS.items():
+        model, _ = _round(uh, agg, rounds[0])
+        holder, want = hold(model), held_bytes(hold(ref.fedavg_combine(rounds[0])[0]))
+        del model
+        for ups in rounds[1:7]:
+            _same(_round(uh, agg, ups)[0], ref.fedavg_combine(ups)[0])
+        assert np.array_equal(held_bytes(holder), want), kind
+        del holder
+    # ... and through a reference cycle nothing else reaches, until the collector takes it
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        model, _ = _round(uh, agg, rounds[0])
+        want = ref.fedavg_combine(rounds[0])[0]
+        reach = [weakref.ref(a) for a in model]       # to read the bytes without holding them
+        cycle = [model]
+        cycle.append(cycle)
+        del model, cycle
+        for ups in rounds[1:7]:
+            _same(_round(uh, agg, ups)[0], ref.fedavg_combine(ups)[0])
+        _same([r() for r in reach], want)
+        gc.collect()
+        assert all(r() is None for r in reach)
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def test_other_dtype_or_shape_goes_general_in_fifo_order(monkeypatch):
@@ -238,6 +270,34 @@ def test_small_fedopt_round_is_the_oracle(K, opt, monkeypatch):
         assert uh.model_updates.qsize() == 0 and all(k.startswith("g") for k in uh.store.models)   # updates deleted
         old = model                          # held by the caller: its block must not be reused
     assert seen == {"small": 3, "general": 0}
+
+
+def test_held_fedopt_models_are_never_overwritten(monkeypatch):
+    """Six rounds of one session (more than the pool keeps blocks), every returned model held: each is
+    still its round's oracle result at the end, and once they are dropped a block comes back."""
+    rng = np.random.default_rng(97)
+    base = [rng.standard_normal(s).astype(np.float32) for s in MNIST]
+    uh, agg = _opt_agg()
+    seen = _opt_spy(monkeypatch)
+    st = ref.FedOptState()
+
+    def one_round(r):
+        ups = _models(rng, MNIST, 2)
+        gid = uh.put_global_model(base, f"g{r}")
+        for a, n in ups:
+            uh.submit(a, n, model_id=gid)
+        model, _ = agg.combine_models(helper=None)
+        return model, ref.fedopt_combine(st, ups, base)[0]
+    held = [one_round(r) for r in range(6)]
+    for model, want in held:
+        _same(model, want)
+    ptrs = {model[0].__array_interface__["data"][0] for model, _ in held}
+    assert len(ptrs) == 6                    # six live models, six blocks
+    del held, model
+    model, want = one_round(6)
+    _same(model, want)
+    assert model[0].__array_interface__["data"][0] in ptrs
+    assert seen == {"small": 7, "general": 0}
 
 
 def test_small_fedopt_goes_general_on_another_layout(monkeypatch):

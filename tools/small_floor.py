@@ -150,11 +150,12 @@ def main():
     from fedn_amd import smallround
     from fedn_amd.layout import Layout
     sess = smallround.SmallSession(dev, Layout.of(cl[0]))
+    admit = lambda u, k: sess.admit(sess.plan, u, sess.arena_ptr + k * sess.stride, sess.window)  # noqa: E731
     for k, u in enumerate(cl):
-        sess.wait(sess.admit(u, k))
-    blk = sess.result_block()
+        sess.wait(admit(u, k))
+    blk = sess.blocks.lease(sess.stride)
     out["fold_host_k2_us"] = med(lambda: sess.fold(blk, 2, [0.0, float(ns[1])], [1.0, float(ns[0] + ns[1])], 0))
-    out["admit_us"] = med(lambda: sess.wait(sess.admit(cl[1], 1)))
+    out["admit_us"] = med(lambda: sess.wait(admit(cl[1], 1)))
     # FedOpt K = 2 (adam) through the plug-in and FEDn's loop restated, the same updates
     uh3 = MemoryUpdateHandler()
     gid = uh3.put_global_model(base, "g0")
