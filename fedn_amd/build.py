@@ -1,4 +1,5 @@
 """Build libfedagg.so (gfx950) in-tree with hipcc. ``python -m fedn_amd.build [--force]``."""
+import glob
 import os
 import shutil
 import subprocess
@@ -7,9 +8,6 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "fedagg.hip")
-ORDER_SRC = os.path.join(HERE, "csrc", "order_mean.h")   # k_order_mean (fa_trimmed_mean), included by SRC
-PAIR_SRC = os.path.join(HERE, "csrc", "pair_dist.h")     # k_pair_sqdist (fa_pairwise_sqdist), included by SRC
-WMEAN_SRC = os.path.join(HERE, "csrc", "wmean_dist.h")   # k_wmean_dist (fa_weighted_mean_sqdist), included by SRC
 HDR = os.path.join(ROOT, "include", "fedagg.h")
 OUT = os.path.join(HERE, "libfedagg.so")
 PROBE_HDR = os.path.join(ROOT, "include", "fedagg_probe.h")
@@ -35,6 +33,13 @@ NPZ_SAVEZ = os.path.join(HERE, "csrc", "savez.cpp")        # numpy-identical wri
 NPZ_PDEFLATE = os.path.join(HERE, "csrc", "pdeflate.h")    # its single-stream parallel deflate
 NPZ_GUARD = os.path.join(HERE, "csrc", "fnpz_guard.h")      # no exception across the C ABI
 NPZ_OUT = os.path.join(HERE, "libfednpz.so")
+
+
+def hip_sources():
+    """SRC and the headers it includes: every csrc/*.h that is not the codec's (the kernel families,
+    their launch policy, the probes). A new header is picked up without an edit here."""
+    codec = {NPZ_INFLATE, NPZ_PDEFLATE, NPZ_GUARD}
+    return [SRC] + sorted(h for h in glob.glob(os.path.join(HERE, "csrc", "*.h")) if h not in codec)
 
 
 def _stale(out, *deps):
@@ -93,8 +98,7 @@ def build(force=False, verbose=True):
 
 def build_hip(force=False, verbose=True, probe=False):
     out = PROBE_OUT if probe else OUT
-    deps = (SRC, ORDER_SRC, PAIR_SRC, WMEAN_SRC, HDR, PROBE_HDR)
-    if not force and not _stale(out, *deps):
+    if not force and not _stale(out, *hip_sources(), HDR, PROBE_HDR):
         return out
     tmp = out + ".tmp"
     cmd = [hipcc()] + FLAGS + (["-DFEDAGG_PROBES"] if probe else []) + ["-I", os.path.join(ROOT, "include"),

@@ -1,7 +1,7 @@
 // order_mean.h — coordinate-wise trimmed mean / median over K client buffers (fa_trimmed_mean).
 //
-// Included by fedagg.hip inside its anonymous namespace (it uses that file's element types, strip
-// loads / stores and error plumbing). With FA_ORDER_NET_ONLY defined only the comparator network is
+// Included by fedagg.hip inside its anonymous namespace (it uses fold_rules.h's element types and strip
+// loads / stores, host_common.h's grid_for and that file's error plumbing). With FA_ORDER_NET_ONLY defined only the comparator network is
 // compiled, by any C++17 compiler: tests/test_robust_host.py checks it with the 0-1 principle.
 //
 // Per element: the K values become unsigned keys whose integer order is the rule's total order

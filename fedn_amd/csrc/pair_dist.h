@@ -1,7 +1,7 @@
 // pair_dist.h — pairwise squared distances of K client buffers (fa_pairwise_sqdist, kernel k_pair_sqdist).
 //
-// Included by fedagg.hip inside its anonymous namespace (it uses that file's element types and error
-// plumbing). D[i][j] = sum_p (C(u_i[p]) - C(u_j[p]))^2 in the compute type C of the dtype family:
+// Included by fedagg.hip inside its anonymous namespace (it uses fold_rules.h's element types and that file's
+// error plumbing). D[i][j] = sum_p (C(u_i[p]) - C(u_j[p]))^2 in the compute type C of the dtype family:
 // f32 for f32 / f16 / bf16 (widened exactly), f64 for f64 / i32 / i64 (one rounding). DESIGN.md §3.8 has
 // the definition, the error bound and the resource table.
 //
@@ -284,7 +284,11 @@ k_pair_finish(double* __restrict__ D, const double* __restrict__ work, const int
     }
 }
 
-inline bool pair_family64(int dtype) { return dtype == FA_F64 || dtype == FA_I32 || dtype == FA_I64; }
+// the compute family of an update dtype: 32 (f32 / f16 / bf16), 64 (f64 / i32 / i64), 0 for any other dtype
+inline int pair_family(int dtype) {
+    if (dtype == FA_F32 || dtype == FA_F16 || dtype == FA_BF16) return 32;
+    return dtype == FA_F64 || dtype == FA_I32 || dtype == FA_I64 ? 64 : 0;
+}
 
 // f(PairGeom-carrying tag) for the (family, KP) of (dtype, K)
 template <typename C, typename F>

@@ -2,7 +2,7 @@
 // (fa_weighted_mean_sqdist, kernel k_wmean_dist): one smoothed Weiszfeld step of the geometric median.
 //
 // Included by fedagg.hip inside its anonymous namespace, after pair_dist.h (it uses that file's
-// conversions, 16-byte loads and fused multiply-add, and fedagg.hip's element types and error plumbing).
+// conversions, 16-byte loads and fused multiply-add, fold_rules.h's element types and fedagg.hip's error plumbing).
 // With C the compute type of the dtype family (f32 for f32 / f16 / bf16, f64 for f64 / i32 / i64) and
 // b_k = C(beta[k]):
 //     z[p] = O(((b_a C(u_a[p]) + b_b C(u_b[p])) + ...))   over the clients with b_k != 0, in index order,

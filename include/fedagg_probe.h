@@ -46,7 +46,7 @@ int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_t
  * pattern probes. fa_tune answers FA_EINVAL for an unknown knob or a value outside the ranges below.
  *
  * Launch geometry of the fp32 / bf16 -> fp32 FedAvg fold (the sweep of tools/microbench.py):
- *   STRIPS x UNROLL x NT: see probe_fedavg_geometry in fedagg.hip for the instantiated
+ *   STRIPS x UNROLL x NT: see probe_fedavg_geometry in csrc/probes.h for the instantiated
  *   combinations; any other runs 1 strip x 8 clients ahead.                                    */
 enum fa_tune_knob {
     FA_TUNE_STRIPS = 0 /* 16-B strips per lane: 1 | 2 | 4 (default) | 8 | 16 */,

@@ -1,4 +1,4 @@
-"""fp64 t/N without a division (CF64::div in fedagg.hip): q0 = RN(t*r), r = RN(1/N) from the
+"""fp64 t/N without a division (CF64::div in fold_rules.h): q0 = RN(t*r), r = RN(1/N) from the
 host, then two Markstein corrections q <- RN(q + RN(t - q*N)*r) computed with FMAs.
 
 The claim is that the result equals RN(t/N) for |t| in [2^-600, 2^600] and

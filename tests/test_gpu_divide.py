@@ -1,4 +1,4 @@
-"""Exhaustive check of the fp32 division shortcut (CF32::fold_strip in fedagg.hip).
+"""Exhaustive check of the fp32 division shortcut (CF32::fold_strip in fold_rules.h).
 
 For every binary32 bit pattern t (all 2^32, NaNs and infinities included) and a set of
 divisors N, the fused FedAvg kernel computes x + (1*(t - x))/N with x = 0, i.e. RN(t/N)

@@ -1,5 +1,5 @@
 """The FedAvg geometry sweep of the probe library (fa_tune STRIPS / UNROLL / NT / LANETAB / BLOCK /
-NT_STORE / NARROW / GRID; probe_fedavg_geometry in fedagg.hip) against the oracle, in full, bit for bit.
+NT_STORE / NARROW / GRID; probe_fedavg_geometry in probes.h) against the oracle, in full, bit for bit.
 
 Every geometry the sweep table instantiates folds fp32 and bf16 updates into an fp32 aggregate at
 the smallest shapes at which these kernels can still go wrong, with AUTO_GEOM 0 so that the knobs

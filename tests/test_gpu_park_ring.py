@@ -1,5 +1,5 @@
 """The generalised parked fold's client ring and parked-tile FIFO (fedavg_park_body<DEPTH, SLOTS> in
-fedagg.hip, k_fedavg_park): DEPTH client buffers in the load ring (the load cursor runs
+fedavg_kernels.h, k_fedavg_park): DEPTH client buffers in the load ring (the load cursor runs
 DEPTH - 1 stream positions ahead of the consume cursor, across tile boundaries), SLOTS parked tiles
 per workgroup in LDS.
 

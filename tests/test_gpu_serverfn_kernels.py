@@ -41,7 +41,7 @@ from oracle import numpy_ref as ref
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-PIPE_MIN_BYTES = 160 << 20       # kPipeMinClientBytes in fedn_amd/csrc/fedagg.hip (not exported)
+PIPE_MIN_BYTES = 160 << 20       # kPipeMinClientBytes in fedn_amd/csrc/fedavg_launch.h (not exported)
 PAIRS = [("f32", "f32"), ("f32", "f64"), ("f64", "f64"), ("f64", "f32")]     # (update, accumulator)
 NP_DT = {"f32": np.float32, "f64": np.float64}
 TORCH_DT = {"f32": torch.float32, "f64": torch.float64}

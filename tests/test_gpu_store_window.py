@@ -1,4 +1,4 @@
-"""The chip-wide store window (fedagg.hip avg_store_window / opt_store_window) moves
+"""The chip-wide store window (fedavg_launch.h avg_store_window / fedopt_launch.h opt_store_window) moves
 stores in time only: the windowed kernels (k_fedavg_pipe_win, k_fedopt_cw) return the unwindowed
 kernels' bits. Compared through the probe library, whose fa_tune knobs switch the window off (-1) or
 leave the product's own choice (0), at sizes where the product picks a window (>= 2^24 elements; FedOpt

@@ -1,4 +1,4 @@
-"""The store-window kernels (k_fedavg_pipe_win, k_fedopt_cw; fedagg.hip) against the
+"""The store-window kernels (k_fedavg_pipe_win, k_fedopt_cw; fedavg_kernels.h, fedopt_kernels.h) against the
 oracle, in full, bit for bit.
 
 The product launches them for large models only (avg_store_window / opt_store_window), where the

@@ -1,4 +1,4 @@
-"""Store-window mode 3, "parked" (fedavg_park_body in fedagg.hip): a persistent grid whose
+"""Store-window mode 3, "parked" (fedavg_park_body in fedavg_kernels.h): a persistent grid whose
 workgroups park a finished tile in LDS, go on to their next tile and store the parked one when the
 window opens.
 

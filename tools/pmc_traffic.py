@@ -26,8 +26,14 @@ def file_sha(path):
 
 
 def kernel_sha():
-    """sha256 (16 hex) of fedn_amd/csrc/fedagg.hip (informational)."""
-    return file_sha(os.path.join(ROOT, "fedn_amd", "csrc", "fedagg.hip"))
+    """sha256 (16 hex) over fedn_amd/csrc/fedagg.hip and the headers it includes, in the build's own
+    order (fedn_amd.build.hip_sources) (informational)."""
+    from fedn_amd.build import hip_sources
+    h = hashlib.sha256()
+    for path in hip_sources():
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
 
 
 def lib_sha(session=None):
@@ -118,7 +124,7 @@ def record_rank(session, world, R=8, sub=None):
     from tools.pmc_rank_fold import rank_geometry
     C, rounds, L = rank_geometry(100_000_000, world, R)
     d = os.path.join(session, sub or f"pmcrank{world}")
-    # the product's geometry rule (fedagg.hip kPipeMinClientBytes, bench.fold_kernel_label)
+    # the product's geometry rule (fedavg_launch.h kPipeMinClientBytes, bench.fold_kernel_label)
     kernel = "k_fedavg_pipe<float, float" if C * 4 >= 160 << 20 else "k_fedavg<float, float"
     fetch, nf = per_launch(os.path.join(d, "pmc_FETCH_SIZE", "run_counter_collection.csv"), kernel)
     write, nw = per_launch(os.path.join(d, "pmc_WRITE_SIZE", "run_counter_collection.csv"), kernel)
