@@ -136,6 +136,10 @@ int fa_fedavg_fold(void* agg, int agg_dtype, const void* const* updates, int upd
     if (int_first && !(n[1] == std::floor(n[1]) && std::fabs(n[1]) < 0x1p63))
         return fail(FA_EINVAL, "fa_fedavg_fold: integer updates need an integral n[1] (got %g); a float "
                                "num_examples folds through fa_elementwise(FA_EW_IFOLD)", n[1]);
+    // ... and in the update dtype: numpy refuses a python int outside it (OverflowError), it never wraps one
+    if (int_first && upd_dtype == FA_I32 && !(n[1] >= -0x1p31 && n[1] < 0x1p31))
+        return fail(FA_EINVAL, "fa_fedavg_fold: int32 updates need an n[1] within int32 (got %.17g); numpy "
+                               "refuses that product (OverflowError)", n[1]);
     if (upd_dtype == FA_F32 && agg_dtype == FA_F32) return launch_fedavg<float, float, CF32>(agg, updates, n, N, K, P, init, false, st);
     if (upd_dtype == FA_BF16 && agg_dtype == FA_F32) return launch_fedavg<bf16, float, CF32>(agg, updates, n, N, K, P, init, false, st);
     if (upd_dtype == FA_F16 && agg_dtype == FA_F16) return launch_fedavg<f16, f16, CF16>(agg, updates, n, N, K, P, init, false, st);

@@ -43,16 +43,10 @@ import torch
 
 import fedopt_cases as fc
 from golden_io import assert_lists_identical
+from guarded_buf import TORCH_DT, Buf
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
-GUARD = 64
-TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32, "f64": torch.float64,
-            "i32": torch.int32, "i64": torch.int64}
-_INT_VIEW = {2: torch.int16, 4: torch.int32, 8: torch.int64}
-_NP_INT = {2: np.int16, 4: np.int32, 8: np.int64}
-SENTINEL = {2: 0x7DAD, 4: 0x7FA5A5A5, 8: 0x7FF5A5A5A5A5A5A5}      # NaNs no computation here produces
 P0, K0 = 2819, 6
 _REF = {}
 
@@ -72,34 +66,6 @@ def _cached(key, make):
     if key not in _REF:
         _REF[key] = make()
     return _REF[key]
-
-
-# ---- guarded device buffers ------------------------------------------------------------------------
-class Buf:
-    """P elements at a 16-B aligned address (+ ``shift`` elements), 64 sentinel elements on each side."""
-
-    def __init__(self, P, name, shift=0, data=None):
-        tdt = TORCH_DT[name]
-        self.P, self.lo = P, GUARD + shift
-        self.full = torch.empty(GUARD + shift + P + GUARD, dtype=tdt, device=DEV)
-        self.size = self.full.element_size()
-        self.full.view(_INT_VIEW[self.size]).fill_(SENTINEL[self.size])
-        self.t = self.full[self.lo:self.lo + P]
-        assert self.t.data_ptr() % 16 == (shift * self.size) % 16
-        if data is not None:
-            h = torch.from_numpy(np.ascontiguousarray(data))
-            self.t.copy_(h.to(tdt) if name == "bf16" else h)
-
-    def check(self, what, written):
-        bits = self.full.view(_INT_VIEW[self.size]).cpu().numpy()
-        s = _NP_INT[self.size](SENTINEL[self.size])
-        assert (bits[:self.lo] == s).all() and (bits[self.lo + self.P:] == s).all(), f"{what}: a guard was written"
-        if written:
-            left = int((bits[self.lo:self.lo + self.P] == s).sum())
-            assert left == 0, f"{what}: {left} of {self.P} elements were not written"
-
-    def numpy(self):
-        return self.t.cpu().numpy()
 
 
 def _shift(shifts, name):
