@@ -115,7 +115,10 @@ struct CF16 {            // numpy half loops: op in float, round to half after e
     __device__ static __forceinline__ V rh(float a) { return f16_to_f32(f32_to_f16(a)); }
     __device__ static __forceinline__ V fold(V x, V y, S n, S N, double) {
         V t = rh(y - x);
-        t = rh(n * t);
+        // n and t are halves, so the half product rounds the exact product once, as rh(n * t) would; written as
+        // a half multiply because the float one is compiled to a mixed-precision fma with a +0 addend, which
+        // turns a product of -0 (a negative or zero n) into +0
+        t = (float)((_Float16)n * (_Float16)t);
         t = rh(t / N);
         return rh(x + t);
     }

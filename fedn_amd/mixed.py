@@ -43,16 +43,24 @@ def _int_fold_kind(d, n):
     """How an integer difference of dtype ``d`` is multiplied by num_examples ``n``
     (numpyhelper.py:32, ``n * (y - x)``): "ifold" in float64 (a float n, or numpy promoting the
     product to float64), "int" in int32 / int64 (the fused kernel's integer first fold), or
-    "nfold" wrapping in a narrow / unsigned dtype (a python int n, weak, takes d's dtype)."""
-    if float_n(n):
-        return "ifold"
-    if d in (np.dtype(np.int32), np.dtype(np.int64)):
-        return "int"
+    "nfold" wrapping in a narrow / unsigned dtype (a python int n, weak, takes d's dtype).
+
+    The product dtype is numpy's own for every d: a numpy-integer n is not weak, so
+    ``np.int64(3) * int32`` is int64 and does not wrap at 32 bits. That product runs as "ifold"
+    while |n| < 2^31 (|n * d| < 2^62 fits int64, and one float64 rounding of the exact product is
+    what numpy's int64 -> float64 conversion before the divide gives); any other product dtype
+    that is neither d nor float64 is refused."""
     p = np.multiply(n, _e(d)).dtype                # raises OverflowError as numpy does
-    if p == np.float64:
+    if p.kind == "f" and p != np.float64:          # np.float32(2.5) * int8 is float32: no such arm
+        raise TypeError(f"a {type(n).__name__} num_examples times a {d} difference ({p}) is not supported")
+    if float_n(n) or p == np.float64:
         return "ifold"
     if p != d:
+        if d == np.int32 and p == np.int64 and abs(int(n)) < 1 << 31:
+            return "ifold"
         raise TypeError(f"a {type(n).__name__} num_examples times a {d} difference ({p}) is not supported")
+    if d in (np.dtype(np.int32), np.dtype(np.int64)):
+        return "int"
     if abs(int(n)) >= 1 << 53:
         raise TypeError(f"num_examples {n} is too large for the {d} fold")
     return "nfold"
@@ -85,7 +93,9 @@ def _e(dt):
 def fold_plan(xs, ys, n, N):
     """numpyhelper.increment_average(x, y, n, N) per tensor pair (numpyhelper.py:32), from
     metadata: [(difference dtype, result dtype, result shape)], zip-truncated. Raises what numpy
-    raises (broadcasting, integer overflow of n/N), and TypeError for dtypes libfedagg lacks."""
+    raises (broadcasting, integer overflow of n/N), and TypeError for dtypes libfedagg lacks, for an
+    integer product no arm computes (_int_fold_kind) and for a numpy-scalar n or N that takes the fold
+    out of the dtype it runs in."""
     plan = []
     for (xshape, xdt), (yshape, ydt) in zip(xs, ys):
         shape = tuple(np.broadcast_shapes(xshape, yshape))
@@ -97,6 +107,13 @@ def fold_plan(xs, ys, n, N):
             raise TypeError(f"unsupported dtypes for the fold: model {xdt}, update {ydt}")
         if d.dtype.kind in "iu":
             _int_fold_kind(d.dtype, n)
+        # every arm computes in the difference's float dtype, or in float64 for an integer difference:
+        # numpy does too for python-scalar n and N (weak), but a numpy scalar can widen the product or
+        # the quotient (np.float32(2.5) * float16 is float32) — refused, never folded in another dtype
+        arm = d.dtype if d.dtype.kind == "f" else np.dtype(np.float64)
+        if t.dtype != arm or r.dtype != arm:
+            raise TypeError(f"a {type(n).__name__} num_examples over a {type(N).__name__} total takes the "
+                            f"{d.dtype} difference to {t.dtype}: not supported")
         plan.append((d.dtype, r.dtype, shape))
     return plan
 
@@ -110,9 +127,18 @@ def float_n(n):
 
 def int_float_n(dtypes, nfolds, n):
     """Whether folding an update with num_examples ``n`` into a running model that is still the
-    first update (``nfolds == 0``) multiplies an INTEGER difference by a float n — the fused
-    kernels fold integer tensors with an integer n only, so such a fold runs per tensor."""
-    return nfolds == 0 and float_n(n) and any(np.dtype(d).kind == "i" for d in dtypes)
+    first update (``nfolds == 0``) multiplies an INTEGER difference outside its own dtype: by a
+    float n (float64), or by a numpy-integer n whose product with the tensor's dtype numpy computes
+    in another dtype (np.int64(3) * int32 is int64). The fused kernels fold integer tensors in the
+    tensor's dtype only, so such a fold runs per tensor."""
+    if nfolds != 0:
+        return False
+    ints = [np.dtype(d) for d in dtypes if np.dtype(d).kind == "i"]
+    if not ints:
+        return False
+    if float_n(n):
+        return True
+    return isinstance(n, np.integer) and any(np.result_type(n, d) != d for d in ints)
 
 
 def sub_plan(ys, olds):
@@ -140,6 +166,14 @@ def _as(t, dtype, shape, stream):
     if t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous():
         return t
     return converted(t, dtype, shape, stream)
+
+
+def _check_casts(shape, *tensors):
+    """Refuse, before anything is launched, an operand ``fa_cast`` could not broadcast to ``shape``
+    (more than 8 non-mergeable dimensions: ops.cast's ValueError)."""
+    for t in tensors:
+        if t is not None and (tuple(t.shape) != tuple(shape) or not t.is_contiguous()):
+            ops.cast_dims(shape, t)
 
 
 def upload(arrays, device, stream):
@@ -209,6 +243,8 @@ class TensorFedAvg:
         """Fold update ``ys`` (device tensors, model order) with num_examples n, running total N."""
         if plan is None:
             plan = fold_plan(self.meta(), meta_of(ys), n, N)
+        for (_, _, shape), x, y in zip(plan, self.x, ys):
+            _check_casts(shape, x, y)
         self.hold.append(ys)                     # inputs stay alive until the round's result
         new = []
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -263,6 +299,10 @@ class TensorFedOpt:
         fplan = None
         if self.acc is not None:
             fplan = fold_plan(self.acc.meta(), [(shape, d) for d, shape in splan], n, N)
+            for (_, _, shape), x in zip(fplan, self.acc.x):
+                _check_casts(shape, x)
+        for (_, shape), y, o in zip(splan, ys, self.old):
+            _check_casts(shape, y, o)
         self.hold.append(ys)
         subs = []
         with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
@@ -299,6 +339,7 @@ class TensorFedOpt:
             if v is not None:
                 shapes.append(tuple(v[i].shape))
             B = tuple(np.broadcast_shapes(*shapes))
+            _check_casts(B, p, o, None if m is None else m[i], None if v is None else v[i])
             if p.dtype not in (torch.float16, torch.float32, torch.float64):
                 raise TypeError(f"pseudo-gradient dtype {p.dtype} is not supported by the server step")
             # a half pg comes from half updates over a half model (numpy's half loops, the kernel's

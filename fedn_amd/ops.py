@@ -132,6 +132,12 @@ def fedavg_fold(agg, updates, n, N, init, stream=None):
         _check_dev(f"updates[{i}]", u, P, dev)
         if u.dtype != upd_dt:
             raise TypeError("all updates in one fold call must share a dtype")
+    # the integer first fold multiplies in the update dtype: numpy's rule for a python int n[1], and for a
+    # numpy integer only when the product keeps that dtype (np.int64(3) * int32 is int64: mixed._int_fold_kind)
+    if init and K > 1 and upd_dt in (torch.int32, torch.int64) and isinstance(n[1], np.integer) \
+            and np.result_type(n[1], numpy_dtype(upd_dt)) != numpy_dtype(upd_dt):
+        raise TypeError(f"a {type(n[1]).__name__} num_examples times a {numpy_dtype(upd_dt)} difference is not "
+                        f"the integer first fold's product")
     with _on(dev):        # launch on the tensors' device (multi-GPU processes)
         st = _stream_handle(agg, stream)
         rc = lib.fa_fedavg_fold(agg.data_ptr(), fa_dtype(agg), _abi.ptr_array([u.data_ptr() for u in updates]),
@@ -520,16 +526,12 @@ def fedopt_step_raw(old_ptr, old_dt, upd_ptrs, upd_dt, n, N, P, *, first, final,
     _abi.check(rc)
 
 
-def cast(out, x, stream=None):
-    """``out[...] = x`` broadcast to ``out.shape`` and widened to ``out.dtype`` (``fa_cast``):
-    numpy's implicit operand preparation for a binary ufunc whose operands differ in dtype or
-    broadcastable shape. ``out`` is contiguous; ``x`` any strided device tensor."""
-    lib = _abi.load()
-    if out.device != x.device:
-        raise ValueError(f"cast: {x.device} -> {out.device}")
-    if not out.is_contiguous():
-        raise ValueError("cast: out must be contiguous")
-    oshape = tuple(out.shape)
+def cast_dims(oshape, x):
+    """The (extents, strides) ``fa_cast`` walks to broadcast the strided device tensor ``x`` to the
+    contiguous shape ``oshape``. Host arithmetic only: raises ValueError where ``x`` does not broadcast to
+    ``oshape``, or where more than 8 dimensions remain after merging (the kernel's limit), so a caller can
+    refuse such an operand before it launches anything."""
+    oshape = tuple(oshape)
     xshape = tuple(x.shape)
     if len(xshape) > len(oshape):
         raise ValueError(f"cast: cannot broadcast {xshape} to {oshape}")
@@ -557,6 +559,20 @@ def cast(out, x, stream=None):
             mt.append(t)
     if len(ms) > 8:
         raise ValueError(f"cast: {len(ms)} non-mergeable dimensions (kernel limit 8)")
+    return ms, mt
+
+
+def cast(out, x, stream=None):
+    """``out[...] = x`` broadcast to ``out.shape`` and widened to ``out.dtype`` (``fa_cast``):
+    numpy's implicit operand preparation for a binary ufunc whose operands differ in dtype or
+    broadcastable shape. ``out`` is contiguous; ``x`` any strided device tensor. A shape that does
+    not broadcast, or more than 8 non-mergeable dimensions, raise ValueError before any launch."""
+    lib = _abi.load()
+    if out.device != x.device:
+        raise ValueError(f"cast: {x.device} -> {out.device}")
+    if not out.is_contiguous():
+        raise ValueError("cast: out must be contiguous")
+    ms, mt = cast_dims(out.shape, x)
     with _on(out.device):
         st = _stream_handle(out, stream)
         rc = lib.fa_cast(out.data_ptr(), fa_dtype(out), x.data_ptr(), fa_dtype(x), len(ms), _abi.int64_array(ms),

@@ -469,6 +469,17 @@ def test_narrow_int_fold_kinds():
     assert mixed._int_fold_kind(np.dtype(np.uint8), 1.0) == "ifold"
     assert mixed._int_fold_kind(np.dtype(np.uint64), np.int64(3)) == "ifold"
     assert mixed._int_fold_kind(np.dtype(np.int32), 3) == "int"
+    # a numpy integer is not weak: np.int64(3) * int32 is int64 and must not wrap at 32 bits — float64 holds
+    # that product exactly while |n| < 2^31 (IFOLD); np.int32(3) keeps int32, np.uint64 makes float64
+    assert mixed._int_fold_kind(np.dtype(np.int32), np.int64(3)) == "ifold"
+    assert mixed._int_fold_kind(np.dtype(np.int32), np.int32(3)) == "int"
+    assert mixed._int_fold_kind(np.dtype(np.int64), np.int64(3)) == "int"
+    assert mixed._int_fold_kind(np.dtype(np.int64), np.uint64(3)) == "ifold"
+    with pytest.raises(TypeError):
+        mixed._int_fold_kind(np.dtype(np.int32), np.int64(1 << 31))
+    with pytest.raises(TypeError):                              # np.float32(2.5) * int8 is float32: no such arm
+        mixed._int_fold_kind(np.dtype(np.int8), np.float32(2.5))
+    assert mixed.int_float_n([np.int32], 0, np.int64(3)) and not mixed.int_float_n([np.int32], 0, np.int32(3))
     with pytest.raises(OverflowError):
         mixed._int_fold_kind(np.dtype(np.int8), 300)
     with pytest.raises(TypeError):
