@@ -161,8 +161,7 @@ class Aggregator(AggregatorBase):
             data["time_model_aggregation"] += time.time() - tic
             nr_aggregated_models -= self._settle(pipe, waiting, delete_models)
             data.update(pipe.timings())
-            if hasattr(pipe, "release"):
-                pipe.release()
+            pipe.release()
         data["nr_aggregated_models"] = nr_aggregated_models
         logger.info("AGGREGATOR({}): Aggregation completed, aggregated {} models.".format(self.name, nr_aggregated_models))
         return model, data

@@ -152,7 +152,7 @@ class Aggregator(AggregatorBase):
                     logger.error(f"Error processing model update: {e}. Skipping this update.")
                     logger.error(traceback.format_exc())
                     if nr_aggregated_models == 0:
-                        if pipe is not None and hasattr(pipe, "quiesce"):
+                        if pipe is not None:
                             pipe.quiesce()          # its pack of the global model reads model_old
                         pipe, small = None, False
                     continue
@@ -167,8 +167,7 @@ class Aggregator(AggregatorBase):
             model = pipe.server_step(self.state, parameters)
             data["time_model_aggregation"] += time.time() - tic
             data.update(pipe.timings())
-            if hasattr(pipe, "release"):
-                pipe.release()
+            pipe.release()
         except Exception as e:  # noqa: BLE001 — fedopt.py:111-116
             data["nr_aggregated_models"] = nr_aggregated_models - self._settle(pipe, waiting, delete_models)
             logger.error(f"Error during model aggregation: {e}")

@@ -319,3 +319,25 @@ class Layout:
             v = flat[off:off + sz]
             out[i] = (np.array(v) if copy else v).reshape(self.shapes[i])
         return out
+
+
+def old_members(layout, old_arrays):
+    """The global model (fedopt.py:89-94) per update dtype group, WITHOUT concatenating it:
+    {group: (dtype, [(flat member array, element offset in the group)])}. Same checks and
+    messages as staging.old_groups."""
+    if len(old_arrays) != len(layout.shapes):
+        raise ValueError("global model and update have different tensor counts")
+    out = {}
+    for dt in layout.groups:
+        parts = []
+        for i, off in layout.members[dt]:
+            o = np.asarray(old_arrays[i])
+            if tuple(o.shape) != layout.shapes[i]:
+                raise ValueError(f"operands could not be combined: tensor {i} has shape {o.shape}, "
+                                 f"global model has {layout.shapes[i]}")
+            parts.append((np.ascontiguousarray(o).reshape(-1), off))
+        odt = {p.dtype for p, _ in parts}
+        if len(odt) != 1:
+            raise TypeError("global-model tensors of one update dtype group must share a dtype")
+        out[dt] = (list(odt)[0], parts)
+    return out

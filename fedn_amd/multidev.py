@@ -32,11 +32,11 @@ import time
 import numpy as np
 import torch
 
-from . import mixed, ops, reuse
+from . import mixed, ops, reuse, staging
 from .ingest import ShardedStagedModel, StagedModel, _member_spans
 from .layout import Layout
-from .staging import (BATCH, HostStreamer, check_fedopt_dtypes, chunks, fused_fedopt_pair, group_tensors, old_members,
-                      state_dtypes)
+from .roundcore import FedAvgRound, FedOptRound, Round
+from .staging import FedOptState, HostStreamer, chunks, group_tensors, state_dtypes
 
 # host tensors at least this large that are page-locked already (pinned memory: e.g. what
 # fedn_amd.helper decodes large npz members into) are DMA'd slice by slice straight from where they lie
@@ -141,11 +141,13 @@ def _host_arrays(arrays):
     return arrays.host if isinstance(arrays, (StagedModel, ShardedStagedModel)) else arrays
 
 
-class _ShardedStaging:
-    """Host slots packed once, each device's slice of every group copied over its own link; or
-    updates already sliced over these devices (ShardedStagedModel), used in place."""
+class _ShardedStaging(Round):
+    """The staging and geometry of several devices under the round protocol (roundcore.Round): host
+    slots packed once, each device's slice of every group copied over its own link; or updates
+    already sliced over these devices (ShardedStagedModel), used in place."""
 
     def __init__(self, devices, layout, nslots):
+        super().__init__()
         self.devices = [torch.device(d) for d in devices]
         self.layout = layout
         self.bounds, self.dev_off, self.dev_bytes = layout.shard_geometry(len(self.devices))
@@ -166,9 +168,6 @@ class _ShardedStaging:
         self.dslots = None
         self._next = 0
         self.reserved = set()
-        self.pending = []                              # resident updates not folded yet: (model, n, N, tag)
-        self.skipped = []                              # (tag, exception): see staging._Pipeline.skipped
-        self.broken = None
         # resident updates read by enqueued launches: kept until the pipeline (the round) ends, as
         # staging._Pipeline._hold does. Dropped when their fold is merely enqueued, their HBM went
         # back to torch's allocator and a staging worker could refill it (H2D on its own stream)
@@ -176,46 +175,17 @@ class _ShardedStaging:
         # update's bytes (GPU test test_multidevice_sharded_ingest_fedavg[3-70], round 5)
         self._hold = []
 
-    def take_skipped(self):
-        out, self.skipped = self.skipped, []
-        return out
+    # ---- what the round protocol asks of the geometry (roundcore.Round) ----------------
+    def _parts(self, get):
+        return [(dv, self.compute[d], {dt: get(d, dt) for dt in self.layout.groups})
+                for d, dv in enumerate(self.devices)]
 
-    def unsettled(self):
-        return len(self.pending)
-
-    def _check_broken(self):
-        if self.broken is not None:
-            raise RuntimeError(f"a batched fold failed and could not be recovered: {self.broken}") from self.broken
+    def _nlaunch(self):
+        return len(self.devices) * len(self.layout.groups)
 
     def _sync_all(self):
         for st in (*self.compute, *self.copy, *self.d2h):
             st.synchronize()
-
-    def _copy_aside(self, per_dev):
-        """Device copies of ``per_dev`` ([{group: tensor}] per device) on each compute stream
-        (staging.NO_SNAPSHOT when HBM cannot hold them: see staging._Pipeline._snapshot)."""
-        from .staging import NO_SNAPSHOT
-        out = []
-        try:
-            for d, dv in enumerate(self.devices):
-                with torch.cuda.device(dv), torch.cuda.stream(self.compute[d]):
-                    out.append({dt: t.clone() for dt, t in per_dev[d].items()})
-        except torch.cuda.OutOfMemoryError:
-            return NO_SNAPSHOT
-        return out
-
-    def _copy_back(self, per_dev, snap):
-        from .staging import NO_SNAPSHOT
-        if snap is NO_SNAPSHOT:
-            self.broken = RuntimeError("a multi-launch fold failed part-way and the aggregate could not be "
-                                       "copied aside beforehand (HBM full): the round is lost")
-            raise self.broken
-        if snap is None:
-            return
-        for d, dv in enumerate(self.devices):
-            with torch.cuda.device(dv), torch.cuda.stream(self.compute[d]):
-                for dt, t in snap[d].items():
-                    per_dev[d][dt].copy_(t)
 
     def _ensure_slots(self):
         if self.host is None:
@@ -224,7 +194,7 @@ class _ShardedStaging:
             self.dslots = [[_DevSlot(self.dev_bytes[d], self.devices[d]) for _ in range(self.nslots)]
                            for d in range(len(self.devices))]
             # fresh HBM from each compute stream's pool: its previous owners' queued work there runs
-            # before the copy streams' H2D overwrite it (staging._Pipeline.stage)
+            # before the copy streams' H2D overwrite it (as staging._Pipeline.stage orders a fresh slot)
             for d in range(len(self.devices)):
                 self.copy[d].wait_stream(self.compute[d])
 
@@ -431,7 +401,7 @@ class _ShardedStaging:
                 "time_stage_host": self.time_stage_host, "time_stage_wait": self.time_stage_wait}
 
 
-class ShardedFedAvgPipeline(_ShardedStaging):
+class ShardedFedAvgPipeline(FedAvgRound, _ShardedStaging):
     """FedAvgPipeline over ``devices`` (a list; the same device may repeat, e.g. in tests)."""
 
     def __init__(self, devices, first_arrays, nslots=3):
@@ -445,17 +415,8 @@ class ShardedFedAvgPipeline(_ShardedStaging):
             self.first = self._stage(first_arrays)
             self.reserved = {self.first}
         self.first_arrays = first_arrays
-        self.nfolds = 0
         self.agg_started = False
         self.agg = [dict() for _ in self.devices]
-        self.general = None
-
-    def _state_meta(self):
-        lay = self.layout
-        if self.nfolds == 0:
-            return list(zip(lay.shapes, lay.dtypes))
-        return [(sh, mixed.np_dtype(ops.fold_result_dtype(ops.torch_dtype(d), ops.torch_dtype(d))))
-                for sh, d in zip(lay.shapes, lay.dtypes)]
 
     def _enter_general(self):
         """Continue the round per tensor on the first device (mixed.TensorFedAvg)."""
@@ -469,17 +430,7 @@ class ShardedFedAvgPipeline(_ShardedStaging):
 
     def add(self, arrays, n, N, tag=None):
         self._check_broken()
-        if self.general is None and (not self.compatible(arrays) or
-                                     mixed.int_float_n(self.layout.dtypes, self.nfolds, n) or
-                                     mixed.per_tensor_dtypes(self.layout.dtypes)):
-            plan = mixed.fold_plan(self._state_meta(), self.meta_of(arrays), n, N)   # raises as numpy
-            self._enter_general()
-            self.general.fold(self.tensors_of(arrays), n, N, plan=plan)
-            self.nfolds += 1
-            return
-        if self.general is not None:
-            self.general.fold(self.tensors_of(arrays), n, N)
-            self.nfolds += 1
+        if self._add_general(arrays, n, N):
             return
         resident = self._resident(arrays)
         if not resident:
@@ -489,39 +440,17 @@ class ShardedFedAvgPipeline(_ShardedStaging):
         if resident:
             self._accept(arrays)
             self.pending.append((arrays, n, N, tag))
-            if len(self.pending) >= BATCH:
+            if len(self.pending) >= staging.BATCH:
                 self._flush()
         else:
             self._flush()
             s = self._stage(arrays)
             try:
-                self._fold_all([(s, n, N)])     # all-or-nothing: the caller skips the update on failure
+                self._fold_batch([(s, n, N)])   # all-or-nothing: the caller skips the update on failure
             finally:
                 for d in range(len(self.devices)):
                     self.dslots[d][s].consumed.record(self.compute[d])
         self.nfolds += 1
-
-    def _snapshot(self):
-        """The aggregate slices copied aside before a continuation fold of several launches (see
-        staging.FedAvgPipeline._snapshot); None when a failed fold cannot leave it half-advanced."""
-        if not self.agg_started or len(self.devices) * len(self.layout.groups) <= 1:
-            return None
-        return self._copy_aside([{dt: self._agg(d, dt) for dt in self.layout.groups} for d in range(len(self.devices))])
-
-    def _restore(self, snap):
-        self._copy_back([{dt: self._agg(d, dt) for dt in self.layout.groups} for d in range(len(self.devices))], snap)
-
-    def _refold_singly(self, entries):
-        """A batched fold over ``entries`` failed: one update at a time (fedavg.py:47-78); an update
-        whose own fold fails is skipped and reported, the aggregate left as before it."""
-        for e in entries:
-            try:
-                self._fold_all([e])
-            except ops.FedAggError as ex:
-                self.skipped.append((e[3] if len(e) > 3 else None, ex))
-
-    def _alias(self):
-        return _host_arrays(self.first_arrays)   # `model = model_next` alias (fedavg.py:65-66)
 
     def _agg(self, d, dt):
         if dt not in self.agg[d]:
@@ -551,33 +480,15 @@ class ShardedFedAvgPipeline(_ShardedStaging):
             self.reserved = set()
         self.agg_started = True
 
-    def _fold_all(self, entries):
-        """One fold of ``entries`` on every device and group, all-or-nothing: on a failed launch the
-        aggregate is put back (or stays unstarted) and the FedAggError propagates."""
+    def _launches(self, entries):
+        """One launch per device and group over ``entries`` (roundcore.Round._fold_batch runs them)."""
         init = not self.agg_started
-        snap = None
-        try:
-            snap = self._snapshot()
-            for d in range(len(self.devices)):
-                for dt in self.layout.groups:
-                    lo, hi = self.bounds[dt][d]
+        for d in range(len(self.devices)):
+            for dt in self.layout.groups:
+                lo, hi = self.bounds[dt][d]
+                if hi > lo:
                     self._fold_dev(d, dt, entries, init, 0, hi - lo)
-        except ops.FedAggError:
-            self._restore(snap)
-            raise
-        self._folded()
-
-    def _flush(self):
-        if self.pending:
-            entries, self.pending = self.pending, []
-            try:
-                try:
-                    self._fold_all(entries)
-                except ops.FedAggError:
-                    self._refold_singly(entries)
-            except BaseException as e:          # the batch is lost: never return a model without it
-                self.broken = e
-                raise
+                    yield
 
     def result(self):
         self._check_broken()
@@ -590,21 +501,26 @@ class ShardedFedAvgPipeline(_ShardedStaging):
             return self._alias()                # every fold after the first update was skipped
         init = not self.agg_started
         flats = {}
-        snap = self._snapshot() if entries else None
+        # the last batch runs chunk by chunk: a failed chunk needs the aggregate back
+        snap, ran = None, [0]
         try:
+            snap = self._snapshot(self._nlaunch()) if entries else None
+
+            def fold_counted(d, clo, chi, dt):
+                self._fold_dev(d, dt, entries, init, clo, chi)
+                ran[0] += 1
             for dt in self.layout.groups:
                 t = ops.torch_dtype(dt)
                 fold = None
                 if entries:
-                    fold = lambda d, clo, chi, dt=dt: self._fold_dev(d, dt, entries, init, clo, chi)  # noqa: E731
+                    fold = lambda d, clo, chi, dt=dt: fold_counted(d, clo, chi, dt)  # noqa: E731
                 per_dev = [self._agg(d, dt) for d in range(len(self.devices))]
                 flats[dt] = self._to_host_chunks(dt, per_dev, fold, ops.fold_result_dtype(t, t))
         except ops.FedAggError:
             if not entries:
                 raise
-            self._sync_all()
-            self._restore(snap)
-            self._refold_singly(entries)
+            self._sync_all()                    # what the failed attempt enqueued has run
+            self._recover(entries, snap, ran[0])
             entries = []
             if not self.agg_started:
                 self._sync_all()
@@ -623,24 +539,15 @@ class ShardedFedAvgPipeline(_ShardedStaging):
         return out
 
 
-class ShardedFedOptState:
+class ShardedFedOptState(FedOptState):
     """FedOptState whose m / v are per-device slices: ``m[d][dt]`` is device d's slice. After a
     round on the per-tensor path the state is per tensor on the first device (``m_t``/``v_t``)
     and is re-sliced over the devices when a later round's layout allows it."""
 
     def __init__(self, fp32=False):
-        self.m = None
-        self.v = None
-        self.signature = None
-        self.layout = None
+        super().__init__(fp32)
         self.bounds = None
         self.devices = None
-        self.m_t = None
-        self.v_t = None
-        self.fp32 = fp32            # fp32-state mode (staging.FedOptState)
-
-    def reset(self):
-        self.__init__(self.fp32)
 
     def tensors(self, device=None):
         """(m, v) per tensor (model order) on ``device`` (default: the first device), or (None, None)."""
@@ -656,39 +563,25 @@ class ShardedFedOptState:
         return out[0], out[1]
 
     def set_tensors(self, m_t, v_t):
-        self.m = self.v = self.signature = self.layout = self.bounds = self.devices = None
-        self.m_t, self.v_t = m_t, v_t
+        super().set_tensors(m_t, v_t)
+        self.bounds = self.devices = None
 
     def regroup(self, layout, sig, bounds, devices):
-        """Make the sliced form match ``layout`` over ``devices`` (see staging.FedOptState.regroup)."""
-        if self.m is None and self.m_t is None:
+        """Make the sliced form match ``layout`` over ``devices``: FedOptState.regroup, each
+        device then taking its slice of every group."""
+        if self._empty_or_current(sig):
             return True
-        if self.m is not None and self.signature == sig:
-            return True
-        m_t, v_t = self.tensors(devices[0])
-        grouped = group_tensors(layout, m_t, v_t, devices[0])
+        grouped = group_tensors(layout, *self.tensors(devices[0]), devices[0])
         if grouped is None:
             return False
-        m_flat, v_flat = grouped
-        self.m = [{dt: m_flat[dt][bounds[dt][d][0]:bounds[dt][d][1]].to(dv) for dt in layout.groups}
-                  for d, dv in enumerate(devices)]
-        self.v = [{dt: v_flat[dt][bounds[dt][d][0]:bounds[dt][d][1]].to(dv) for dt in layout.groups}
-                  for d, dv in enumerate(devices)]
+        self.m, self.v = ([{dt: flat[dt][bounds[dt][d][0]:bounds[dt][d][1]].to(dv) for dt in layout.groups}
+                           for d, dv in enumerate(devices)] for flat in grouped)
         self.signature, self.layout, self.bounds, self.devices = sig, layout, bounds, list(devices)
         self.m_t = self.v_t = None
         return True
 
-    def _host(self, ts):
-        return None if ts is None else [t.to("cpu").numpy() for t in ts]
 
-    def m_host(self):
-        return self._host(self.tensors()[0])
-
-    def v_host(self):
-        return self._host(self.tensors()[1])
-
-
-class ShardedFedOptPipeline(_ShardedStaging):
+class ShardedFedOptPipeline(FedOptRound, _ShardedStaging):
     """FedOptPipeline (staging.py) over ``devices``: pseudo-gradient fold and server step on
     every device's slice, each with its slice of old / pg / m / v resident in its HBM."""
 
@@ -698,19 +591,7 @@ class ShardedFedOptPipeline(_ShardedStaging):
         else:
             layout = Layout.of(_host_arrays(first_arrays))
         super().__init__(devices, layout, nslots)
-        self.old_arrays = old_arrays
-        self.general = None
-        # see staging.FedOptPipeline: otherwise the round runs per tensor (first device)
-        self.fused_ok = True
-        try:
-            self.old_host = old_members(layout, old_arrays)
-            check_fedopt_dtypes(layout)
-            for dt, (odt, _) in self.old_host.items():
-                if not fused_fedopt_pair(ops.torch_dtype(dt), ops.torch_dtype(odt)):
-                    raise TypeError(f"no fused kernel for {dt} updates over a {odt} global model")
-        except (ValueError, TypeError):
-            self.fused_ok = False
-            self.old_host = {}
+        self._init_fedopt(old_arrays)             # not fused_ok: the round runs per tensor (first device)
         # the global model reaches each device lazily through a pinned ring: whole (when a host
         # update must fold into pg) or chunk by chunk inside the server step (H2D || step || D2H)
         self.old = []
@@ -721,15 +602,8 @@ class ShardedFedOptPipeline(_ShardedStaging):
                 per[dt] = torch.empty(hi - lo, dtype=ops.torch_dtype(odt), device=dv)
             self.old.append(per)
             self.copy[d].wait_stream(self.compute[d])   # see _ensure_slots
-        self.old_ready = set()
         self.streamer = HostStreamer()
         self.pg = [dict() for _ in self.devices]
-        self.pg_started = False
-        self.nfolds = 0
-
-    def _pg_meta(self):
-        return [(sh, mixed.np_dtype(ops.fedopt_dtypes(ops.torch_dtype(d), self.old[0][d].dtype, None)[0]))
-                for sh, d in zip(self.layout.shapes, self.layout.dtypes)]
 
     def _enter_general(self):
         """Continue the round per tensor on the first device (mixed.TensorFedOpt)."""
@@ -743,14 +617,7 @@ class ShardedFedOptPipeline(_ShardedStaging):
 
     def add(self, arrays, n, N, tag=None):
         self._check_broken()
-        if self.general is None and not (self.fused_ok and self.compatible(arrays)):
-            splan = mixed.sub_plan(self.meta_of(arrays), mixed.host_meta(self.old_arrays))   # raises as numpy
-            if self.nfolds:
-                mixed.fold_plan(self._pg_meta(), [(sh, d) for d, sh in splan], n, N)
-            self._enter_general()
-        if self.general is not None:
-            self.general.add(self.tensors_of(arrays), n, N)
-            self.nfolds += 1
+        if self._add_general(arrays, n, N):
             return
         resident = self._resident(arrays)
         if not resident:
@@ -758,13 +625,13 @@ class ShardedFedOptPipeline(_ShardedStaging):
         if resident:
             self._accept(arrays)
             self.pending.append((arrays, n, N, tag))
-            if len(self.pending) >= BATCH:
+            if len(self.pending) >= staging.BATCH:
                 self._flush()
         else:
             self._flush()
             s = self._stage(arrays)
             try:
-                self._fold_pg([(s, n, N)])      # all-or-nothing: the caller skips the update on failure
+                self._fold_batch([(s, n, N)])   # all-or-nothing: the caller skips the update on failure
             finally:
                 for d in range(len(self.devices)):
                     self.dslots[d][s].consumed.record(self.compute[d])
@@ -790,82 +657,32 @@ class ShardedFedOptPipeline(_ShardedStaging):
                 self.compute[d].wait_event(self._h2d_old(d, dt, 0, hi - lo))
             self.old_ready.add(dt)
 
-    def _fold_pg(self, entries):
-        """``entries`` into every device's pg slices, all-or-nothing (pg copied aside first when a
-        started pg is continued by several launches); a failed launch's FedAggError propagates."""
-        snap = None
-        if self.pg_started and len(self.devices) * len(self.layout.groups) > 1:
-            snap = self._copy_aside([{dt: self._pg(d, dt) for dt in self.layout.groups} for d in range(len(self.devices))])
-        try:
-            for dt in self.layout.groups:
-                self._old_all(dt)
-                for d in range(len(self.devices)):
-                    lo, hi = self.bounds[dt][d]
-                    pg = self._pg(d, dt)
-                    if hi > lo:
-                        ys = [self._view(d, e[0], dt) for e in entries]
-                        ops.fedopt_step(self.old[d][dt], ys, [e[1] for e in entries], [e[2] for e in entries],
-                                        first=not self.pg_started, final=False, pg=pg, stream=self.compute[d])
-        except ops.FedAggError:
-            self._copy_back([{dt: self._pg(d, dt) for dt in self.layout.groups} for d in range(len(self.devices))], snap)
-            raise
-        self.pg_started = True
+    def _launches(self, entries):
+        """``entries`` into every device's pg slices, one launch per group and device
+        (roundcore.Round._fold_batch runs them all-or-nothing)."""
+        for dt in self.layout.groups:
+            self._old_all(dt)
+            for d in range(len(self.devices)):
+                lo, hi = self.bounds[dt][d]
+                pg = self._pg(d, dt)
+                if hi > lo:
+                    ys = [self._view(d, e[0], dt) for e in entries]
+                    ops.fedopt_step(self.old[d][dt], ys, [e[1] for e in entries], [e[2] for e in entries],
+                                    first=not self.pg_started, final=False, pg=pg, stream=self.compute[d])
+                    yield
 
-    def _fold_pg_isolated(self, entries):
-        """A batch into pg; on a failed launch one update at a time (fedopt.py:74-106), skipping and
-        reporting each update whose own fold fails."""
-        try:
-            self._fold_pg(entries)
-            return
-        except ops.FedAggError:
-            pass
-        for e in entries:
-            try:
-                self._fold_pg([e])
-            except ops.FedAggError as ex:
-                self.skipped.append((e[3] if len(e) > 3 else None, ex))
-
-    def _flush(self):
-        if self.pending:
-            entries, self.pending = self.pending, []
-            try:
-                self._fold_pg_isolated(entries)
-            except BaseException as e:          # the batch is lost: never return a model without it
-                self.broken = e
-                raise
-
-    def server_step(self, state, params):
-        opt = params["serveropt"]
-        if opt not in ("adam", "yogi", "adagrad"):
-            raise ValueError(f"Unsupported server optimizer: {opt}")
+    # ---- roundcore.FedOptRound.server_step's hooks --------------------------------------------
+    def _regroup(self, state):
         sig = (self.layout.signature(), tuple(str(d) for d in self.devices))
-        if self.general is None and not state.regroup(self.layout, sig, self.bounds, self.devices):
-            self._enter_general()               # the state's layout differs from this round's
-        if self.general is not None:
-            m, v = state.tensors(self.devices[0])
-            model, m, v = self.general.server_step(m, v, params, fp32=getattr(state, "fp32", False))
-            state.set_tensors(m, v)
-            return model
-        self._check_broken()
-        # per device and group, one fused launch: pending (resident) updates folded into the
-        # pseudo-gradient in registers (FIRST when pg holds nothing yet) and the server step,
-        # chunked so that the global model's H2D, the step and the result's D2H overlap
-        entries, self.pending = self.pending, []
-        if not entries and not self.pg_started:
-            raise ValueError("no update was folded into the pseudo-gradient")   # fedopt.py:110, 117-118
-        old_ready = set(self.old_ready)
-        try:
-            return self._fused_step(state, params, opt, sig, entries)
-        except ops.FedAggError:
-            if not entries:
-                raise                           # the server step itself failed (fedopt.py:111-116)
-        # see staging.FedOptPipeline.server_step: the batch one update at a time, then K = 0
-        self._sync_all()
-        self.old_ready = old_ready
-        self._fold_pg_isolated(entries)
-        return self.server_step(state, params)
+        return sig if state.regroup(self.layout, sig, self.bounds, self.devices) else None
+
+    def _state_tensors(self, state):
+        return state.tensors(self.devices[0])
 
     def _fused_step(self, state, params, opt, sig, entries):
+        """Per device and group, one fused launch: pending (resident) updates folded into the
+        pseudo-gradient in registers and the server step, chunked so that the global model's H2D,
+        the step and the result's D2H overlap."""
         first = not self.pg_started
         ns, Ns = [e[1] for e in entries], [e[2] for e in entries]
         new_m = [dict() for _ in self.devices]
@@ -882,11 +699,11 @@ class ShardedFedOptPipeline(_ShardedStaging):
                 m_in = state.m[d][dt] if state.m is not None else None
                 v_in = state.v[d][dt] if state.v is not None else None
                 m_dt, sdt = state_dtypes(state, dt, old.dtype, m_in)
-                # new m / v buffers: a failed step leaves the session's state untouched (staging.py)
+                # new m / v buffers: a failed step leaves the session's state untouched
                 m_out = torch.empty(P, dtype=m_dt, device=dv)
                 v_out = torch.empty(P, dtype=sdt, device=dv)
                 out = torch.empty(P, dtype=sdt, device=dv)
-                pg = self._pg(d, dt) if (not first or len(entries) > BATCH) else None
+                pg = self._pg(d, dt) if (not first or len(entries) > staging.BATCH) else None
                 new_m[d][dt], new_v[d][dt] = m_out, v_out
                 ctx.append((old, pg, m_in, m_out, v_in, v_out, out))
 

@@ -881,3 +881,23 @@ def host_register_ptr(ptr, nbytes):
 
 def host_unregister_ptr(ptr):
     _abi.check(_abi.load().fa_host_unregister(int(ptr)))
+
+
+_FUSED_OPT = {(torch.float32, torch.float32), (torch.bfloat16, torch.float32), (torch.float32, torch.float64),
+              (torch.float64, torch.float64), (torch.bfloat16, torch.float64), (torch.float64, torch.float32),
+              (torch.int64, torch.int64), (torch.int64, torch.float64), (torch.int64, torch.float32),
+              (torch.int32, torch.int32), (torch.int32, torch.float64), (torch.int32, torch.float32),
+              # float16 sessions: a half global model's pseudo-gradient is half (numpy's half loops)
+              (torch.float16, torch.float16), (torch.float16, torch.float32), (torch.float16, torch.float64),
+              (torch.float32, torch.float16), (torch.float64, torch.float16)}
+
+
+def fused_fedopt_pair(upd, old):
+    """Whether fa_fedopt_step instantiates (update dtype, global-model dtype)."""
+    return (upd, old) in _FUSED_OPT
+
+
+def check_fedopt_dtypes(layout):
+    for dt in layout.groups:
+        if torch_dtype(dt) not in (torch.float16, torch.float32, torch.float64, torch.int32, torch.int64):
+            raise TypeError(f"FedOpt supports float16/float32/float64/int32/int64 updates, got {dt}")

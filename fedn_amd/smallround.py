@@ -298,7 +298,7 @@ class _Round:
         if self.ticket is not None:
             self.s.wait(self.ticket)
             self.ticket = None
-        if self.fallback is not None and hasattr(self.fallback, "quiesce"):
+        if self.fallback is not None:
             self.fallback.quiesce()
 
     def _replay(self, pipe):
@@ -308,8 +308,7 @@ class _Round:
             for arrays, n, N, tag in self.held:
                 pipe.add(arrays, n, N, tag=tag)
         except BaseException:
-            if hasattr(pipe, "quiesce"):        # its packs in flight end before the arrays can go
-                pipe.quiesce()
+            pipe.quiesce()                      # its packs in flight end before the arrays can go
             raise
         return pipe
 
@@ -328,7 +327,7 @@ class _Round:
 
     def release(self):
         self.quiesce()
-        if self.fallback is not None and hasattr(self.fallback, "release"):
+        if self.fallback is not None:
             self.fallback.release()
 
 

@@ -29,6 +29,9 @@ import torch
 from . import mixed, ops, reuse
 from .ingest import StagedModel
 from .layout import Layout, fast_admission, parallel_copy, start_pack_into, wait_pack_jobs
+from .layout import old_members  # noqa: F401 (re-exported)
+from .ops import check_fedopt_dtypes, fused_fedopt_pair  # noqa: F401 (re-exported)
+from .roundcore import NO_SNAPSHOT, FedAvgRound, FedOptRound, Round  # noqa: F401 (NO_SNAPSHOT re-exported)
 
 
 BATCH = 64                    # device-resident updates folded per launch (the kernarg client table)
@@ -185,11 +188,12 @@ def _addr(src):
     return src.ptr if type(src) is _ArenaRef else src.dev.data_ptr()
 
 
-NO_SNAPSHOT = object()   # _snapshot could not copy the aggregate aside (HBM full)
+class _Pipeline(Round):
+    """One device's staging and geometry under the round protocol (roundcore.Round): slots, arenas,
+    streams, and the addresses a launch reads."""
 
-
-class _Pipeline:
     def __init__(self, device, layout, nslots, slots=None, streams=None, cache=None, batch=True):
+        super().__init__()
         self.device = torch.device(device)
         self.layout = layout
         self.compute = torch.cuda.current_stream(self.device)
@@ -213,7 +217,6 @@ class _Pipeline:
         self.time_pack = 0.0
         self.time_d2h = 0.0
         self._hold = []
-        self.pending = []                        # device-resident updates not folded yet: (staged, n, N)
         # small host updates are batched through arenas; ``batch=False`` on the helper path
         # (helper.Helper.increment_average folds ONE pair per pipeline: an arena there would be
         # allocated for a single update and never reused)
@@ -243,25 +246,6 @@ class _Pipeline:
         self._copy_used = False                  # work was enqueued on the copy stream this round
         self._d2h_used = False                   # ... on the d2h stream
         self.streamer = kept["streamer"] if kept else HostStreamer()
-        # per-update failure isolation (fedavg.py:75-78, fedopt.py:103-106): updates admitted into a
-        # batch whose multi-client launch failed are refolded one at a time; (tag, exception) of each
-        # one whose own fold failed, for the aggregator to log, uncount and keep in storage
-        self.skipped = []
-        self.broken = None                       # a batch lost beyond recovery: result() raises it
-
-    def take_skipped(self):
-        """(tag, exception) of the updates skipped since the last call (see ``skipped``)."""
-        out, self.skipped = self.skipped, []
-        return out
-
-    def unsettled(self):
-        """How many of the most recently added updates are admitted but not folded yet (the pending
-        batch): their fold may still fail, so the aggregator keeps them in storage until then."""
-        return len(self.pending)
-
-    def _check_broken(self):
-        if self.broken is not None:
-            raise RuntimeError(f"a batched fold failed and could not be recovered: {self.broken}") from self.broken
 
     def quiesce(self):
         """Wait for the packs still queued to the native gather thread: its copies read the update
@@ -281,6 +265,21 @@ class _Pipeline:
                             {"slots": self.slots, "arenas": self._arenas, "streams": (self.copy, self.d2h),
                              "streamer": self.streamer})
             self.cache = None
+
+    # ---- what the round protocol asks of the geometry (roundcore.Round) ----------------
+    def _parts(self, get):
+        return [(self.device, self.compute, {dt: get(dt) for dt in self.layout.groups})]
+
+    def _nlaunch(self):
+        return len(self.layout.groups)
+
+    def _sync_all(self):
+        self.compute.synchronize()
+        self.copy.synchronize()
+        self.d2h.synchronize()
+
+    def _before_flush(self):
+        self.upload_arena()                     # also FedAvg's first update, when it waits in the arena
 
     # ---- staging ---------------------------------------------------------------------
     def _take_slot(self):
@@ -560,7 +559,7 @@ class _Pipeline:
         return {"time_h2d": h2d, "time_kernel": kern, "time_pack": self.time_pack, "time_d2h": self.time_d2h}
 
 
-class FedAvgPipeline(_Pipeline):
+class FedAvgPipeline(FedAvgRound, _Pipeline):
     """Streaming FedAvg on one device: fedavg.py:47-71 with the fold on the GPU."""
 
     def __init__(self, device, first_arrays, nslots=3, slots=None, streams=None, cache=None, batch=True):
@@ -581,23 +580,12 @@ class FedAvgPipeline(_Pipeline):
         else:
             self.first = self.stage(first_arrays)
             self.first.reserved = True
-        self.nfolds = 0
         self.agg_started = False                 # agg holds a fold of the first update
         self.agg = {}
-        self.general = None                      # mixed.TensorFedAvg once an update differs in layout
         # the fold chunks of the latest large host update, (dt, lo, hi, event after the chunk) — valid
         # while nothing was folded after it: result() then D2H's each chunk of the model as soon as
         # that chunk is folded, overlapping the rest of the last update's H2D (PCIe is full duplex)
         self._last_fold = None
-
-    def _state_meta(self):
-        """(shape, dtype) per tensor of the running model: the first update's before any fold,
-        numpy's fold result dtype after."""
-        lay = self.layout
-        if self.nfolds == 0:
-            return list(zip(lay.shapes, lay.dtypes))
-        return [(s, mixed.np_dtype(ops.fold_result_dtype(ops.torch_dtype(d), ops.torch_dtype(d))))
-                for s, d in zip(lay.shapes, lay.dtypes)]
 
     def _enter_general(self):
         """Hand the running model to the per-tensor path (mixed.TensorFedAvg)."""
@@ -640,17 +628,7 @@ class FedAvgPipeline(_Pipeline):
                 self._flush()
             self.nfolds += 1
             return
-        if self.general is None and (not self.compatible(arrays) or
-                                     mixed.int_float_n(self.layout.dtypes, self.nfolds, n) or
-                                     mixed.per_tensor_dtypes(self.layout.dtypes)):
-            plan = mixed.fold_plan(self._state_meta(), self.meta_of(arrays), n, N)   # raises as numpy
-            self._enter_general()
-            self.general.fold(self.tensors_of(arrays), n, N, plan=plan)
-            self.nfolds += 1
-            return
-        if self.general is not None:
-            self.general.fold(self.tensors_of(arrays), n, N)
-            self.nfolds += 1
+        if self._add_general(arrays, n, N):
             return
         if isinstance(arrays, StagedModel):
             self.layout.check_layout(arrays.layout)
@@ -675,53 +653,6 @@ class FedAvgPipeline(_Pipeline):
                 slot.consumed.record(self.compute)   # the slot's next H2D waits for what was enqueued
         self.nfolds += 1
 
-    # ---- per-update failure isolation (fedavg.py:75-78) ---------------------------------------
-    def _snapshot(self, launches):
-        """The running aggregate copied aside before a continuation fold of more than one launch:
-        one that fails part-way leaves it half-advanced, and the recovery needs it back. None when
-        not needed: not started (an init fold rewrites it) or one launch (a failed launch ran nothing)."""
-        if not self.agg_started or launches <= 1:
-            return None
-        try:                                    # a model-sized clone for the fold's duration (the HBM
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):   # budget's headroom)
-                return {dt: self._agg(dt).clone() for dt in self.layout.groups}
-        except torch.cuda.OutOfMemoryError:
-            return NO_SNAPSHOT                  # the fold goes ahead; only a failure part-way is fatal
-
-    def _restore(self, snap, ran=1):
-        """Put the aggregate back after a failed multi-launch fold of which ``ran`` launches had been
-        enqueued (0: the aggregate is untouched, nothing to put back)."""
-        if ran == 0:
-            return
-        if snap is NO_SNAPSHOT:
-            # a launch failed after earlier ones advanced the aggregate, and HBM held no copy of it:
-            # the round cannot go on with this update skipped (ADVICE r4) — result() raises
-            self.broken = RuntimeError("a multi-launch fold failed part-way and the aggregate could not be "
-                                       "copied aside beforehand (HBM full): the round is lost")
-            raise self.broken
-        if snap is not None:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                for dt, t in snap.items():
-                    self._agg(dt).copy_(t)
-
-    def _refold_singly(self, entries):
-        """A multi-client launch over ``entries`` failed: fold them one at a time in FIFO order as
-        FEDn does (fedavg.py:47-78). An update whose own fold fails is skipped and reported with its
-        tag; its examples stay counted (its N is already in every later entry's running total), and
-        the aggregate is as the previous update left it (each update's launches are all-or-nothing)."""
-        for e in entries:
-            snap, ran = None, 0
-            try:
-                snap = self._snapshot(len(self.layout.groups))
-                for dt in self.layout.groups:
-                    self._fold_group(dt, [e], not self.agg_started, 0, self.layout.group_elems[dt])
-                    ran += 1
-            except ops.FedAggError as ex:
-                self._restore(snap, ran)
-                self.skipped.append((e[3] if len(e) > 3 else None, ex))
-                continue
-            self._folded()
-
     def _fold_pieces(self, slot, n, N):
         """Fold one staged host update on arrival, one launch per H2D piece of each group, each
         waiting only for its piece (the fold of piece j overlaps the DMA of piece j + 1); the chunks'
@@ -741,21 +672,19 @@ class FedAvgPipeline(_Pipeline):
                     bounds[-1] = (bounds[-1][0], P)
             plan += [(dt, off, isz, lo, hi) for lo, hi in bounds]
         done = []
-        snap = None
-        try:
-            snap = self._snapshot(len(plan))    # this update's launches are all-or-nothing
+
+        def launches():
             for dt, off, isz, lo, hi in plan:
                 self.wait_bytes(slot, off + lo * isz, off + hi * isz)
                 self._fold_group(dt, [(slot, n, N)], init, lo, hi)
                 ev = torch.cuda.Event()
                 ev.record(self.compute)
                 done.append((dt, lo, hi, ev))
-        except ops.FedAggError:
-            self._last_fold = None
-            self._restore(snap, len(done))      # the update is skipped by the caller (fedavg.py:75-78)
-            raise
-        self._end_span(span)
-        self._folded()
+                yield
+            self._end_span(span)
+        self._last_fold = None
+        # this update's launches are all-or-nothing: on a failure the caller skips it (fedavg.py:75-78)
+        self._all_or_nothing(len(plan), launches())
         self._last_fold = done
 
     def _fold_group(self, dt, entries, init, lo, hi):
@@ -789,33 +718,15 @@ class FedAvgPipeline(_Pipeline):
             self.first.reserved = False
         self.agg_started = True
 
-    def _fold_all(self, entries):
+    def _launches(self, entries):
+        """One launch per group over ``entries`` (roundcore.Round._fold_batch runs them)."""
         self._last_fold = None
         span = self._kernel_span()
         init = not self.agg_started
-        snap, ran = None, 0
-        try:
-            snap = self._snapshot(len(self.layout.groups))
-            for dt in self.layout.groups:
-                self._fold_group(dt, entries, init, 0, self.layout.group_elems[dt])
-                ran += 1
-        except ops.FedAggError:
-            self._restore(snap, ran)
-            self._refold_singly(entries)
-            self._end_span(span)
-            return
+        for dt in self.layout.groups:
+            self._fold_group(dt, entries, init, 0, self.layout.group_elems[dt])
+            yield
         self._end_span(span)
-        self._folded()
-
-    def _flush(self):
-        self.upload_arena()                     # also the first update, when it waits in the arena
-        if self.pending:
-            entries, self.pending = self.pending, []
-            try:
-                self._fold_all(entries)
-            except BaseException as e:          # the batch is lost: never return a model without it
-                self.broken = e
-                raise
 
     def result(self):
         """The aggregated model as a new host ``list[np.ndarray]`` (fedavg.py:83). A pending
@@ -862,8 +773,7 @@ class FedAvgPipeline(_Pipeline):
                 raise
             self.compute.synchronize()          # what the failed attempt enqueued has run
             self.d2h.synchronize()
-            self._restore(snap, ran[0])
-            self._refold_singly(entries)
+            self._recover(entries, snap, ran[0])
             entries = []
             if not self.agg_started:
                 self.compute.synchronize()
@@ -882,11 +792,6 @@ class FedAvgPipeline(_Pipeline):
         for dt in self.layout.groups:
             self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
         return out
-
-    def _alias(self):
-        """The first update itself: the model when nothing was folded into it (fedavg.py:65-66)."""
-        first = self.first_arrays
-        return first.host if isinstance(first, StagedModel) else first
 
     def _zero_copy_result(self):
         """A small round that never left the host: the first update and every pending one wait in the
@@ -985,7 +890,6 @@ class AndroidFedAvgPipeline(_Pipeline):
         first = np.asarray(first_arrays)
         super().__init__(device, Layout.of([first]), 2)
         self.first_arrays = first_arrays
-        self.nfolds = 0
         self.g = None
 
     def add(self, arrays, n, N, tag=None):
@@ -1052,18 +956,19 @@ class FedOptState:
         """Make the fused form match ``layout``: True if it does (or the state is empty), False
         if the per-tensor state cannot be grouped that way (shapes differ, or one group would
         need two m dtypes) — then the round's server step runs per tensor."""
-        if self.m is None and self.m_t is None:
+        if self._empty_or_current(sig):
             return True
-        if self.m is not None and self.signature == sig:
-            return True
-        m_t, v_t = self.tensors()
-        grouped = group_tensors(layout, m_t, v_t, device)
+        grouped = group_tensors(layout, *self.tensors(), device)
         if grouped is None:
             return False
         self.m, self.v = grouped
         self.signature, self.layout = sig, layout
         self.m_t = self.v_t = None
         return True
+
+    def _empty_or_current(self, sig):
+        """Nothing to regroup: no state yet, or it is in the fused form ``sig`` names already."""
+        return (self.m is None and self.m_t is None) or (self.m is not None and self.signature == sig)
 
     def _host(self, ts):
         if ts is None:
@@ -1120,48 +1025,6 @@ def old_groups(layout, old_arrays):
     return out
 
 
-def old_members(layout, old_arrays):
-    """The global model (fedopt.py:89-94) per update dtype group, WITHOUT concatenating it:
-    {group: (dtype, [(flat member array, element offset in the group)])}. Same checks and
-    messages as old_groups."""
-    if len(old_arrays) != len(layout.shapes):
-        raise ValueError("global model and update have different tensor counts")
-    out = {}
-    for dt in layout.groups:
-        parts = []
-        for i, off in layout.members[dt]:
-            o = np.asarray(old_arrays[i])
-            if tuple(o.shape) != layout.shapes[i]:
-                raise ValueError(f"operands could not be combined: tensor {i} has shape {o.shape}, "
-                                 f"global model has {layout.shapes[i]}")
-            parts.append((np.ascontiguousarray(o).reshape(-1), off))
-        odt = {p.dtype for p, _ in parts}
-        if len(odt) != 1:
-            raise TypeError("global-model tensors of one update dtype group must share a dtype")
-        out[dt] = (list(odt)[0], parts)
-    return out
-
-
-_FUSED_OPT = {(torch.float32, torch.float32), (torch.bfloat16, torch.float32), (torch.float32, torch.float64),
-              (torch.float64, torch.float64), (torch.bfloat16, torch.float64), (torch.float64, torch.float32),
-              (torch.int64, torch.int64), (torch.int64, torch.float64), (torch.int64, torch.float32),
-              (torch.int32, torch.int32), (torch.int32, torch.float64), (torch.int32, torch.float32),
-              # float16 sessions: a half global model's pseudo-gradient is half (numpy's half loops)
-              (torch.float16, torch.float16), (torch.float16, torch.float32), (torch.float16, torch.float64),
-              (torch.float32, torch.float16), (torch.float64, torch.float16)}
-
-
-def fused_fedopt_pair(upd, old):
-    """Whether fa_fedopt_step instantiates (update dtype, global-model dtype)."""
-    return (upd, old) in _FUSED_OPT
-
-
-def check_fedopt_dtypes(layout):
-    for dt in layout.groups:
-        if ops.torch_dtype(dt) not in (torch.float16, torch.float32, torch.float64, torch.int32, torch.int64):
-            raise TypeError(f"FedOpt supports float16/float32/float64/int32/int64 updates, got {dt}")
-
-
 def state_dtypes(state, upd_dt, old_dt, m_in):
     """(m dtype, v / new-model dtype) of one group's server step: numpy's flow (m promoted, v and the
     model float64, fedopt.py:151-258), or in the fp32-state mode, for a float32 global model, float32
@@ -1172,43 +1035,21 @@ def state_dtypes(state, upd_dt, old_dt, m_in):
     return m_dt, torch.float64
 
 
-class FedOptPipeline(_Pipeline):
+class FedOptPipeline(FedOptRound, _Pipeline):
     """Streaming FedOpt on one device: the pseudo-gradient loop of fedopt.py:74-106 on the
     GPU (pg resident in HBM), then the fused server step (fedopt.py:151-258)."""
 
     def __init__(self, device, old_arrays, first_arrays, nslots=2, cache=None):
         layout = first_arrays.layout if isinstance(first_arrays, StagedModel) else Layout.of(first_arrays)
         super().__init__(device, layout, nslots, cache=cache)
-        self.old_arrays = old_arrays
-        self.nfolds = 0
+        self._init_fedopt(old_arrays)
         self.pg = {}
-        self.pg_started = False                  # pg holds a partial pseudo-gradient
-        self.general = None                      # mixed.TensorFedOpt once an update differs in layout
-        self.old_ready = set()
-        # the fused path needs the global model to share the update's shapes with one dtype per
-        # update-dtype group, and a (update, old) dtype pair the kernel instantiates; otherwise
-        # the round runs on the per-tensor path (numpy promotion / broadcasting, mixed.py)
-        self.fused_ok = True
-        try:
-            self.old_host = old_members(layout, old_arrays)
-            check_fedopt_dtypes(layout)
-            for dt, (odt, _) in self.old_host.items():
-                if not fused_fedopt_pair(ops.torch_dtype(dt), ops.torch_dtype(odt)):
-                    raise TypeError(f"no fused kernel for {dt} updates over a {odt} global model")
-        except (ValueError, TypeError):
-            self.fused_ok = False
-            self.old_host = {}
         # the global model reaches HBM lazily: whole (when a host update must fold into pg) or
         # chunk by chunk inside the server step's pipeline (H2D || step || D2H)
         self.old = {dt: torch.empty(layout.group_elems[dt], dtype=ops.torch_dtype(odt), device=self.device)
                     for dt, (odt, _) in self.old_host.items()}
         if self.old:
             self.copy.wait_stream(self.compute)  # their HBM's previous owners' queued work first (stage())
-
-    def _pg_meta(self):
-        """(shape, dtype) per tensor of the pseudo-gradient folded so far (fused layout)."""
-        return [(s, mixed.np_dtype(ops.fedopt_dtypes(ops.torch_dtype(d), self.old[d].dtype, None)[0]))
-                for s, d in zip(self.layout.shapes, self.layout.dtypes)]
 
     def _enter_general(self):
         """Hand the round to the per-tensor path (mixed.TensorFedOpt): pending updates are folded
@@ -1248,15 +1089,7 @@ class FedOptPipeline(_Pipeline):
                 self._flush()
             self.nfolds += 1
             return
-        if self.general is None and not (self.fused_ok and self.compatible(arrays)):
-            ym = self.meta_of(arrays)
-            splan = mixed.sub_plan(ym, mixed.host_meta(self.old_arrays))          # raises as numpy
-            if self.nfolds:
-                mixed.fold_plan(self._pg_meta(), [(sh, d) for d, sh in splan], n, N)
-            self._enter_general()
-        if self.general is not None:
-            self.general.add(self.tensors_of(arrays), n, N)
-            self.nfolds += 1
+        if self._add_general(arrays, n, N):
             return
         if isinstance(arrays, StagedModel):
             self.pending.append((self.acquire(arrays), n, N, tag))
@@ -1271,7 +1104,7 @@ class FedOptPipeline(_Pipeline):
             self._flush()
             slot = self.acquire(arrays)
             try:
-                self._fold_pg([(slot, n, N)])   # fails as a whole: the caller skips the update
+                self._fold_batch([(slot, n, N)])   # fails as a whole: the caller skips the update
             finally:
                 slot.consumed.record(self.compute)
         self.nfolds += 1
@@ -1310,58 +1143,21 @@ class FedOptPipeline(_Pipeline):
             self.old_ready.add(dt)
         return self.old[dt]
 
-    def _fold_pg(self, entries):
-        """Fold ``entries`` into pg (no server step): one launch per group over the entries' device
-        addresses (arena pieces, slots and staged models on this device: no tensor view per update).
-        All-or-nothing: on a failed launch pg is as before the call (copied aside first when the
-        groups' launches continue a started pg) and the FedAggError propagates."""
+    def _launches(self, entries):
+        """``entries`` into pg (no server step): one launch per group over the entries' device
+        addresses (arena pieces, slots and staged models on this device: no tensor view per update);
+        roundcore.Round._fold_batch runs them all-or-nothing."""
         span = self._kernel_span()
         ns, Ns = [e[1] for e in entries], [e[2] for e in entries]
         addrs = [_addr(e[0]) for e in entries]
-        snap = None
-        if self.pg_started and len(self.layout.groups) > 1:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                snap = {dt: self._pg(dt).clone() for dt in self.layout.groups}
-        try:
-            for dt in self.layout.groups:
-                old = self._old_dev(dt)
-                off = self.layout.group_byte_offset[dt]
-                ops.fedopt_step_raw(old.data_ptr(), old.dtype, [p + off for p in addrs], ops.torch_dtype(dt), ns, Ns,
-                                    old.numel(), first=not self.pg_started, final=False,
-                                    pg_ptr=self._pg(dt).data_ptr(), stream=self.compute, device=self.device)
-        except ops.FedAggError:
-            if snap is not None:
-                with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                    for dt, t in snap.items():
-                        self._pg(dt).copy_(t)
-            raise
+        for dt in self.layout.groups:
+            old = self._old_dev(dt)
+            off = self.layout.group_byte_offset[dt]
+            ops.fedopt_step_raw(old.data_ptr(), old.dtype, [p + off for p in addrs], ops.torch_dtype(dt), ns, Ns,
+                                old.numel(), first=not self.pg_started, final=False,
+                                pg_ptr=self._pg(dt).data_ptr(), stream=self.compute, device=self.device)
+            yield
         self._end_span(span)
-        self.pg_started = True
-
-    def _fold_pg_isolated(self, entries):
-        """Fold a batch into pg; if its launch fails, fold its updates one at a time as FEDn does
-        (fedopt.py:74-106): an update whose own fold fails is skipped and reported with its tag (its
-        examples stay counted), the rest fold in FIFO order."""
-        try:
-            self._fold_pg(entries)
-            return
-        except ops.FedAggError:
-            pass
-        for e in entries:
-            try:
-                self._fold_pg([e])
-            except ops.FedAggError as ex:
-                self.skipped.append((e[3] if len(e) > 3 else None, ex))
-
-    def _flush(self):
-        if self.pending:
-            self.upload_arena()
-            entries, self.pending = self.pending, []
-            try:
-                self._fold_pg_isolated(entries)
-            except BaseException as e:          # the batch is lost: never return a model without it
-                self.broken = e
-                raise
 
     def _zero_copy_step(self, state, params, opt, sig):
         """A small round that never left the host (see FedAvgPipeline._zero_copy_result): every update
@@ -1370,6 +1166,7 @@ class FedOptPipeline(_Pipeline):
         global model from a pinned block through their device addresses and writes the new model into
         the caller's pinned block (m / v stay in HBM) — the same kernel, so the same bits — then one
         synchronize. None if not such a round."""
+        self._tic = tic = time.perf_counter()    # the server step's start (also _fused_step's)
         a = self._arena
         entries = self.pending
         if (self.pg_started or a is None or a.uploaded or not entries or len(entries) > BATCH
@@ -1430,51 +1227,18 @@ class FedOptPipeline(_Pipeline):
         model = [None] * len(self.layout.shapes)
         for dt in self.layout.groups:
             self.layout.unpack_group(hosts[dt].numpy(), dt, model, copy=False)
+        self.time_d2h += time.perf_counter() - tic
         return model
 
-    def server_step(self, state, params):
-        """Apply adam/yogi/adagrad (fedopt.py:139-258); returns the new model (host, f64)."""
-        opt = params["serveropt"]
-        if opt not in ("adam", "yogi", "adagrad"):
-            raise ValueError(f"Unsupported server optimizer: {opt}")
+    # ---- roundcore.FedOptRound.server_step's hooks --------------------------------------------
+    def _regroup(self, state):
         sig = self.layout.signature()
-        if self.general is None and not state.regroup(self.layout, sig, self.device):
-            self._enter_general()               # the state's layout differs from this round's
-        if self.general is not None:
-            m, v = state.tensors()
-            model, m, v = self.general.server_step(m, v, params, fp32=getattr(state, "fp32", False))
-            state.set_tensors(m, v)
-            return model
-        self._check_broken()
-        tic = time.perf_counter()
-        model = self._zero_copy_step(state, params, opt, sig)
-        if model is not None:
-            self.time_d2h += time.perf_counter() - tic
-            return model
-        # one fused launch per group: the pending (device-resident) updates, if any, folded into
-        # the pseudo-gradient in registers (FIRST when pg holds nothing yet) and the server
-        # step; chunked so that each chunk's D2H of the new model overlaps the next chunk
-        self.upload_arena()
-        entries, self.pending = self.pending, []
-        if not entries and not self.pg_started:
-            # every update's fold was skipped: no pseudo-gradient (fedopt.py:110, 117-118)
-            raise ValueError("no update was folded into the pseudo-gradient")
-        old_ready = set(self.old_ready)
-        try:
-            return self._fused_step(state, params, opt, sig, entries, tic)
-        except ops.FedAggError:
-            if not entries:
-                raise                           # the server step itself failed (fedopt.py:111-116)
-        # the fused launch failed: the pending updates fold into pg one at a time (a failing one is
-        # skipped), then the server step runs alone (K = 0); its failure is the round's (None, data)
-        self.compute.synchronize()
-        self.copy.synchronize()
-        self.d2h.synchronize()
-        self.old_ready = old_ready              # a global model streamed in part-way is streamed again
-        self._fold_pg_isolated(entries)
-        return self.server_step(state, params)
+        return sig if state.regroup(self.layout, sig, self.device) else None
 
-    def _fused_step(self, state, params, opt, sig, entries, tic):
+    def _state_tensors(self, state):
+        return state.tensors()
+
+    def _fused_step(self, state, params, opt, sig, entries):
         first = not self.pg_started
         new_m, new_v, hosts = {}, {}, {}
         span = self._kernel_span()
@@ -1516,7 +1280,7 @@ class FedOptPipeline(_Pipeline):
         if self._d2h_used or not self._d2h_on_compute:
             self.d2h.synchronize()
         self._synced = self._d2h_on_compute and not self._d2h_used and not self._copy_used
-        self.time_d2h += time.perf_counter() - tic
+        self.time_d2h += time.perf_counter() - self._tic
         state.m, state.v, state.signature, state.layout = new_m, new_v, sig, self.layout
         model = [None] * len(self.layout.shapes)
         for dt in self.layout.groups:

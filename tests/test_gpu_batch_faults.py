@@ -129,6 +129,42 @@ def test_fedavg_batched_failure_skips_only_the_failing_update(route, shapes, K, 
         assert hits, "the poisoned launch was never issued"
 
 
+def test_fedavg_sliced_batches_are_flushed_at_the_patched_batch_size(monkeypatch):
+    """``staging.BATCH`` is read at call time on the sliced route too: patched to 3, no launch holds
+    more than 3 clients (seen at the poisoned launches, which record their table's length), and the
+    round is the oracle's with the poisoned updates skipped."""
+    from fedn_amd import multidev, staging  # noqa: F401 — loaded before the patch, as in a running process
+    from fedn_amd.aggregators.fedavg import Aggregator
+    _setup("staged_sliced", monkeypatch)
+    monkeypatch.setattr(staging, "BATCH", 3)
+    K, bad = 8, [2, 6]
+    rng = np.random.default_rng(K * 31 + bad[0])
+    base = [rng.standard_normal(s).astype(np.float32) for s in SMALL]
+    ups, ns = _clients(rng, SMALL, K, base)
+    Ns = np.cumsum(ns)
+    uh, st = _handlers("staged_sliced")
+    try:
+        agg = Aggregator(st, devices=[DEV, DEV])
+        for u, n in zip(ups, ns):
+            uh.submit(u, n, via=st)
+        hits = _poison(monkeypatch, {(float(ns[p]), float(Ns[p])) for p in bad})
+        model, data = agg.combine_models(helper=None)
+    finally:
+        st.close()
+
+    def increment(m1, m2, n, N):
+        if any(m2 is ups[p] for p in bad):
+            raise RuntimeError("fold failed")
+        return ref.increment_average(m1, m2, n, N)
+
+    want, nr = ref.fedavg_combine(list(zip(ups, ns)), increment)
+    assert nr == data["nr_aggregated_models"] == K - len(bad)
+    assert_lists_identical(model, want, f"fedavg sliced BATCH 3 skipping {bad}")
+    # init launches carry the first update in the table too: at most 1 + 3 entries
+    assert hits and max(k for _, k in hits) <= 4, f"a launch held more than BATCH clients: {hits}"
+    assert any(k >= 3 for _, k in hits), f"the poisoned updates were never folded in a batch: {hits}"
+
+
 OPT_CASES = [("host", SMALL, 6, [2]), ("host_nozc", SMALL, 6, [0]), ("host_flush", SMALL, 8, [1, 6]),
              ("staged", SMALL, 6, [3]), ("staged_large", LARGE, 5, [4]), ("staged_sliced", SMALL, 6, [2]),
              ("staged_k70", SMALL, 70, [5, 65])]
@@ -281,3 +317,119 @@ def test_snapshot_that_cannot_be_taken_only_matters_on_failure(route, monkeypatc
         finally:
             if st is not None:
                 st.close()
+
+
+def _no_room_for_clones(monkeypatch):
+    """HBM full for every copy-aside: ``clone`` of a device tensor raises torch's out-of-memory error
+    (the pipelines clone nothing else), so every snapshot reports staging.NO_SNAPSHOT."""
+    asked = []
+    real = torch.Tensor.clone
+
+    def clone(self, *a, **kw):
+        if self.is_cuda:
+            asked.append(self.numel())
+            raise torch.cuda.OutOfMemoryError("injected: no room for the copy aside")
+        return real(self, *a, **kw)
+    monkeypatch.setattr(torch.Tensor, "clone", clone)
+    return asked
+
+
+def _fail_int64_launch_of(monkeypatch, pair):
+    """The int64 group's launch of every fold that holds the (n, N) ``pair`` raises FedAggError: the
+    update's second launch, after its float32 group's launch was enqueued."""
+    from fedn_amd import _abi, ops
+    hits = []
+    for name in FOLD_OPS:
+        real = getattr(ops, name)
+        sig = inspect.signature(real)
+
+        def wrapper(*a, _real=real, _sig=sig, _name=name, **kw):
+            args = _sig.bind(*a, **kw).arguments
+            upd = args.get("upd_dtype") or args.get("upd_dt")
+            if upd is None and args.get("updates"):
+                upd = args["updates"][0].dtype
+            if upd == torch.int64 and any((float(x), float(y)) == pair for x, y in zip(args["n"], args["N"])):
+                hits.append(_name)
+                raise _abi.FedAggError(_abi.FA_EHIP, f"{_name}: injected failure of the second launch")
+            return _real(*a, **kw)
+
+        monkeypatch.setattr(ops, name, wrapper)
+    return hits
+
+
+def test_sliced_snapshot_that_cannot_be_taken_only_matters_on_failure(monkeypatch):
+    """test_snapshot_that_cannot_be_taken_only_matters_on_failure on the sliced route (two entries of
+    one device): u1-u3 fold as the init batch, u4-u5 continue it in result()."""
+    from fedn_amd import staging
+    from fedn_amd.aggregators.fedavg import Aggregator
+    _setup("staged_sliced", monkeypatch)
+    monkeypatch.setattr(staging, "BATCH", 3)
+    asked = _no_room_for_clones(monkeypatch)
+    for poisoned in (False, True):
+        rng = np.random.default_rng(77)
+        ups, ns = _mixed_updates(rng, 6)
+        uh, st = _handlers("staged_sliced")
+        try:
+            agg = Aggregator(st, devices=[DEV, DEV])
+            for u, n in zip(ups, ns):
+                uh.submit(u, n, via=st)
+            if not poisoned:
+                model, data = agg.combine_models(helper=None)
+                want, nr = ref.fedavg_combine(list(zip(ups, ns)))
+                assert data["nr_aggregated_models"] == nr == 6
+                assert_lists_identical(model, want, "sliced without a snapshot")
+                assert asked, "no multi-launch fold ran: the case does not exercise the snapshot"
+            else:
+                hits = _fail_int64_launch_of(monkeypatch, (float(ns[4]), float(np.cumsum(ns)[4])))
+                with pytest.raises(RuntimeError, match="could not be copied aside"):
+                    agg.combine_models(helper=None)
+                assert hits, "the failing launch was never issued"
+        finally:
+            st.close()
+
+
+@pytest.mark.parametrize("route", ["staged", "staged_sliced"])
+def test_fedopt_snapshot_that_cannot_be_taken_only_matters_on_failure(route, monkeypatch):
+    """The same for FedOpt's pseudo-gradient, on one device and sliced: round 1 of an adam session
+    runs with every copy-aside refused and is the oracle's bit for bit (u0-u2 start pg, u3-u5
+    continue it behind a snapshot); in round 2 the int64 launch of a continuing update fails after
+    its float32 launch ran. That cannot be undone: the add that flushed the batch raises, the update
+    is logged and skipped as fedopt.py:103-106 does, the server step refuses the lost round, and
+    combine_models returns (None, data) (fedopt.py:111-116) with m / v still round 1's."""
+    from fedn_amd import staging
+    from fedn_amd.aggregators.fedopt import Aggregator
+    _setup(route, monkeypatch)
+    monkeypatch.setattr(staging, "BATCH", 3)
+    asked = _no_room_for_clones(monkeypatch)
+    rng = np.random.default_rng(78)
+    ups, ns = _mixed_updates(rng, 6)
+    old = [u.copy() for u in ups[0]]             # the global model: float32, float32, int64
+    state = ref.FedOptState()
+    uh, st = _handlers(route)
+    try:
+        agg = Aggregator(st, devices=[DEV, DEV]) if "sliced" in route else Aggregator(st, device=DEV)
+        gid = uh.put_global_model(old, "g0")
+        for u, n in zip(ups, ns):
+            uh.submit(u, n, model_id=gid, via=st)
+        model, data = agg.combine_models(helper=None)
+        want, nr = ref.fedopt_combine(state, list(zip(ups, ns)), old)
+        assert data["nr_aggregated_models"] == nr == 6
+        assert_lists_identical(model, want, f"fedopt {route} without a snapshot")
+        assert_lists_identical(agg.m, state.m, "m")
+        assert_lists_identical(agg.v, state.v, "v")
+        assert asked, "no multi-launch fold continued pg: the case does not exercise the snapshot"
+
+        old = [want[0].astype(np.float32), want[1].astype(np.float32), want[2].astype(np.int64)]
+        ups, ns = _mixed_updates(rng, 6)
+        gid = uh.put_global_model(old, "g1")
+        for u, n in zip(ups, ns):
+            uh.submit(u, n, model_id=gid, via=st)
+        hits = _fail_int64_launch_of(monkeypatch, (float(ns[4]), float(np.cumsum(ns)[4])))
+        model, data = agg.combine_models(helper=None)
+        assert hits, "the failing launch was never issued"
+        assert model is None, "a round whose pseudo-gradient is half-advanced returns no model"
+        assert data["nr_aggregated_models"] == 5, "the add that lost the round is skipped like a failed fold"
+        assert_lists_identical(agg.m, state.m, "m is still round 1's")
+        assert_lists_identical(agg.v, state.v, "v is still round 1's")
+    finally:
+        st.close()

@@ -45,7 +45,7 @@ def main():
     timed(fedavg_mod, "make_fedavg_pipeline", "make_pipeline")
     cls = staging.FedAvgPipeline if a.kind == "fedavg" else staging.FedOptPipeline
     for name in ("__init__", "add", "result", "server_step", "timings", "release", "upload_arena", "_fold_group",
-                 "_fold_then_d2h", "put_small", "_h2d_old", "_fold_pg"):
+                 "_fold_then_d2h", "put_small", "_h2d_old", "_fold_batch"):
         if name in vars(cls) or hasattr(cls, name):
             timed(cls, name, name)
     uh = MemoryUpdateHandler()
