@@ -122,6 +122,12 @@ EXPORTS = {
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double),   # updates, upd_dtype, beta
         ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
         ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
+    "fa_centered_clip_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),     # K, P
+    "fa_centered_clip_step": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,   # out (or NULL), center, out_dtype, dist
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double),   # updates, upd_dtype, coef
+        ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
+        ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -139,9 +145,13 @@ PROBE_EXPORTS = {
         ctypes.c_int, ctypes.c_int,                                        # upd_dtype, K
         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
+    "fa_centered_clip_geometry": (ctypes.c_int, [
+        ctypes.c_int, ctypes.c_int,                                        # upd_dtype, K
+        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+        ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

@@ -67,6 +67,11 @@ class Aggregator(AggregatorBase):
         """Values dropped at each end of the K admitted updates' sorted values."""
         return trim_count(parameters["trim_fraction"], K)
 
+    def prepare_round(self, helper, admitted):
+        """Called before :meth:`reduce_round` with the session's helper and the admitted ModelUpdates
+        (FIFO): a rule that needs more than the updates fetches it here (centeredclip.py: the global
+        model). A failure is a failed round: ``(None, data)``, nothing deleted."""
+
     def reduce_round(self, pipe, K, parameters):
         """The model of the K admitted updates held by ``pipe`` (the rule itself: subclasses override)."""
         return pipe.result(self.trim(K, parameters))
@@ -151,6 +156,7 @@ class Aggregator(AggregatorBase):
             return None, data
         try:
             tic = time.time()
+            self.prepare_round(helper, admitted)
             model = self.reduce_round(pipe, K, parameters)
             data["time_model_aggregation"] += time.time() - tic
             data.update(pipe.timings())

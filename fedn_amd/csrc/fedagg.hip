@@ -90,6 +90,7 @@ size_t dt_size(int dt) {
 #include "order_mean.h"       // coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
+#include "cclip.h"            // one centred-clipping step and the K squared distances to it (k_cclip_dist, fa_centered_clip_step)
 
 }  // namespace
 
@@ -784,6 +785,55 @@ int fa_weighted_mean_sqdist(void* out, int out_dtype, double* dist, const void* 
         case FA_F64: return launch_wmean_dist<double>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
         case FA_I32: return launch_wmean_dist<int32_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
         default: return launch_wmean_dist<int64_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+    }
+}
+
+int64_t fa_centered_clip_work(int K, int64_t P) {
+    if (K < 1 || K > kMaxK || P < 0) return 0;
+    // the dtype with the most workgroups (the smallest tile, the largest grid); kMaxK doubles per workgroup
+    int64_t n = 0;
+    for (const int dt : {FA_F32, FA_F16, FA_BF16, FA_F64, FA_I32, FA_I64}) n = std::max(n, cc_workgroups(P, cc_geom_dt(dt, K)));
+    return std::max<int64_t>(n * kMaxK, 1);
+}
+
+int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* dist, const void* const* updates,
+                          int upd_dtype, const double* coef, int K, int64_t P, int accumulate, double* work, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!dist || !center || !coef || !updates || !work)
+        return fail(FA_EINVAL, "fa_centered_clip_step: null pointer argument");
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_centered_clip_step: K=%d outside 1..%d", K, kMaxK);
+    if (P < 0) return fail(FA_EINVAL, "fa_centered_clip_step: negative size (P=%lld)", (long long)P);
+    const bool f32fam = pair_family(upd_dtype) == 32;
+    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "fa_centered_clip_step: unsupported dtype %d", upd_dtype);
+    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
+    if (out_dtype != want)
+        return fail(FA_EDTYPE, "fa_centered_clip_step: updates of dtype %d move a centre of dtype %d, not %d", upd_dtype,
+                    want, out_dtype);
+    double cc[kMaxK];
+    for (int k = 0; k < K; ++k) {
+        if (!(coef[k] >= 0.0) || std::isinf(coef[k]))
+            return fail(FA_EINVAL, "fa_centered_clip_step: coef[%d]=%g is negative or not finite", k, coef[k]);
+        cc[k] = f32fam ? (double)(float)coef[k] : coef[k];       // C(coef[k]), cast once
+        if (std::isinf(cc[k]))
+            return fail(FA_EINVAL, "fa_centered_clip_step: coef[%d]=%g is not finite in the compute type", k, coef[k]);
+    }
+    if (out && out != center && P > 0) {                     // in place or disjoint, nothing between
+        const uintptr_t a = reinterpret_cast<uintptr_t>(out), b = reinterpret_cast<uintptr_t>(center);
+        const uintptr_t len = (uintptr_t)P * dt_size(want);
+        if (a < b + len && b < a + len)
+            return fail(FA_EINVAL, "fa_centered_clip_step: out and center overlap without being the same buffer");
+    }
+    if (P > 0)                                               // (an empty buffer may be a null pointer)
+        if (const int rc = check_updates("fa_centered_clip_step", updates, K)) return rc;
+    if (accumulate && P == 0) return FA_OK;                  // nothing to add: no launch
+    switch (upd_dtype) {
+        case FA_F32: return launch_cclip_dist<float>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+        case FA_F16: return launch_cclip_dist<f16>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+        case FA_BF16: return launch_cclip_dist<bf16>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+        case FA_F64: return launch_cclip_dist<double>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+        case FA_I32: return launch_cclip_dist<int32_t>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+        default: return launch_cclip_dist<int64_t>(out, center, dist, updates, cc, K, P, accumulate, work, st);
     }
 }
 

@@ -393,6 +393,85 @@ def weighted_mean_sqdist(updates, beta, out=None, dist=None, accumulate=False, s
     return (out if store else None), dist
 
 
+def cclip_geometry(dtype, K):
+    """``(TE, chain, max workgroups, tiles per flush)`` of ``fa_centered_clip_step`` for K updates of
+    ``dtype``, as :func:`wmean_geometry` (its tile holds one more column, the centre's). A measurement
+    entry point (libfedagg_probe.so)."""
+    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _abi.check(_abi.load_probe().fa_centered_clip_geometry(fa_dtype(dtype), int(K), ctypes.byref(te), ctypes.byref(r),
+                                                           ctypes.byref(wg), ctypes.byref(ft)))
+    return te.value, r.value, wg.value, ft.value
+
+
+def centered_clip_step(updates, center, coef, out=None, dist=None, accumulate=False, store=True, stream=None):
+    """One centred-clipping step on device (``fa_centered_clip_step``): the new point
+    ``v' = v + sum_k coef[k] * (u_k - v)`` — the differences to the centre ``v`` taken first, summed in
+    index order in the compute type over the clients with a nonzero coefficient, rounded once to
+    :func:`order_mean_dtype` of the updates' dtype — and the K squared distances ``sum_p (u_k[p] - v'[p])**2``
+    of EVERY update to it, each within :func:`sqdist_rtol` of the exact sum, in one pass that reads every
+    update and the centre once. Returns ``(out or None, dist)``; the same bits on every call.
+
+    updates     1 <= K <= 64 flat device tensors of one dtype (float32 / float64 / float16 / bfloat16 /
+                int32 / int64) and one length
+    center      flat device tensor of :func:`order_mean_dtype` of the updates' dtype, of the same length
+    coef        K coefficients, finite and >= 0; all zero is legal (v' = v: the distances to the centre)
+    out         flat device tensor for v': ``center`` itself (in place) or one that does not overlap it;
+                allocated when None and ``store``
+    dist        K float64 device values; allocated when None
+    accumulate  add this call's distances to ``dist`` instead of writing it (dtype groups, slices)
+    store       False: v' is formed for the distances but not stored (``out`` is left alone; None is returned)
+    """
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"centered_clip_step takes 1..{MAX_ORDER_K} updates, got {K}")
+    if not isinstance(updates[0], torch.Tensor):
+        raise TypeError("updates[0] must be a torch.Tensor")
+    P = updates[0].numel()
+    dev = updates[0].device
+    upd_dt = updates[0].dtype
+    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
+        raise TypeError(f"centered_clip_step: dtype {upd_dt} is not supported")
+    out_dt = order_mean_dtype(upd_dt)
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one centered_clip_step call must share a dtype")
+    _check_dev("center", center, P, dev)
+    if center.dtype != out_dt:
+        raise TypeError(f"centered_clip_step: center must be {out_dt} for {upd_dt} updates, got {center.dtype}")
+    coef = [float(c) for c in coef]
+    if len(coef) != K:
+        raise ValueError(f"centered_clip_step: {len(coef)} coefficients for {K} updates")
+    if out is not None:
+        _check_dev("out", out, P, dev)
+        if out.dtype != out_dt:
+            raise TypeError(f"centered_clip_step: out must be {out_dt} for {upd_dt} updates, got {out.dtype}")
+    if dist is None:
+        if accumulate:
+            raise ValueError("centered_clip_step: accumulate needs the distances to add to (dist)")
+    else:
+        _check_dev("dist", dist, K, dev)
+        if dist.dtype != torch.float64:
+            raise TypeError(f"centered_clip_step: dist must be float64, got {dist.dtype}")
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):               # scratch and fresh outputs belong to the launching stream
+            if out is None and store:
+                out = torch.empty(P, dtype=out_dt, device=dev)
+            if dist is None:
+                dist = torch.empty(K, dtype=torch.float64, device=dev)
+            work = torch.empty(max(1, int(lib.fa_centered_clip_work(K, P))), dtype=torch.float64, device=dev)
+        # (an empty tensor has no address and the library refuses a null centre: at P = 0 nothing reads it)
+        cptr = center.data_ptr() if P else work.data_ptr()
+        rc = lib.fa_centered_clip_step((out.data_ptr() or None) if store else None, cptr, fa_dtype(out_dt),
+                                       dist.data_ptr(), _abi.ptr_array([u.data_ptr() for u in updates]),
+                                       fa_dtype(upd_dt), _abi.double_array(coef), K, P, int(bool(accumulate)),
+                                       work.data_ptr(), ctypes_stream(s))
+    _abi.check(rc)
+    return (out if store else None), dist
+
+
 def running_mean(g, m, a, b, T, stream=None):
     """``g = (g*a + m*b)/T`` in place (``fa_running_mean``): one step of the reference's
     incremental server-function example (sf_incremental_aggregation.py:36-37)."""

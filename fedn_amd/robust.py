@@ -1,5 +1,5 @@
 """Device pipeline of the robust aggregation rules: coordinate-wise trimmed mean and median, the
-selection rules Krum / Multi-Krum, and the geometric median.
+selection rules Krum / Multi-Krum, the geometric median, and centred clipping.
 
 Unlike the FedAvg fold, which sees one client at a time, an order statistic needs all K updates of a
 round at once: per element, the K values are sorted, the ``trim`` smallest and largest dropped and the
@@ -25,6 +25,13 @@ smallest sum of distances to the updates: ``geometric_median(iterations, nu)`` r
 steps, each ONE pass over the held updates that forms the weighted mean and the K distances to it
 (``fa_weighted_mean_sqdist``, kernel ``k_wmean_dist``); the weights of the next step come from the
 distances on the host (:func:`weiszfeld_weights`).
+
+Centred clipping (Karimireddy, He and Jaggi) is the one rule anchored at the previous
+global model ``v``: ``centered_clip(center_arrays, iterations, tau)`` moves ``v`` by the mean of the
+updates' differences to it, each clipped to the norm ``tau``, ``iterations`` times. A step is ONE pass
+over the held updates that forms the new point in place and the K distances to it
+(``fa_centered_clip_step``, kernel ``k_cclip_dist``); the clipping coefficients of the next step come from
+the distances on the host (:func:`clip_coefficients`).
 
 All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
 ``ops.MAX_ORDER_K`` (64) updates per round.
@@ -129,6 +136,27 @@ def weiszfeld_weights(d, nu):
     return w / total
 
 
+def clip_coefficients(d, tau):
+    """The coefficients of one centred-clipping step from the K squared distances ``d`` to the current
+    point, in float64 and in index order: ``r = sqrt(d_k)``, ``lambda_k = 1`` where ``r <= tau`` else
+    ``tau / r``, and 0 where ``r`` is not finite (a non-finite or negative ``d_k``); ``coef_k = lambda_k /
+    K_good`` with ``K_good`` the number of clients with a finite ``r``. Raises ``ValueError`` when there is
+    none."""
+    d = np.asarray(d, dtype=np.float64).reshape(-1)
+    tau = np.float64(tau)
+    lam = np.zeros(d.size, dtype=np.float64)
+    good = 0
+    with np.errstate(invalid="ignore"):
+        for k in range(d.size):
+            r = np.sqrt(d[k])
+            if np.isfinite(r):
+                lam[k] = np.float64(1.0) if r <= tau else tau / r
+                good += 1
+    if good == 0:
+        raise ValueError(f"no client has a finite distance: {d}")
+    return lam / np.float64(good)
+
+
 def _several_devices():
     from .aggregators.fedavg import env_devices
     devs = env_devices()
@@ -161,6 +189,7 @@ class RobustPipeline:
         self.selected, self.scores = None, None     # select_mean: FIFO indices, float64 scores
         self.weights, self.distances = None, None   # geometric_median: the last pass's beta, sqrt(d)
         self.excluded, self.trace = [], []          # ... clients shut out as non-finite; (beta, d) per pass
+        self.coefficients = None                    # centered_clip: the last pass's clipping coefficients
         self.time_pack = 0.0
         self.time_d2h = 0.0
         self.add(first, tag)
@@ -386,6 +415,121 @@ class RobustPipeline:
         self.time_d2h += time.perf_counter() - tic
         self.trace.append((beta, d))
         return d, hosts
+
+    def centered_clip(self, center_arrays, iterations, tau):
+        """Centred clipping of the held updates around the previous global model ``center_arrays``
+        (Karimireddy, He and Jaggi), ``iterations`` steps with radius ``tau``, as host arrays like
+        :meth:`result`'s.
+
+        The centre — arrays of the round's shapes, each tensor of the updates' dtype or of that dtype's
+        ``ops.order_mean_dtype`` — is converted to the latter per dtype group on the host and uploaded
+        ONCE, allocated on the compute stream; it sits outside the budget like the ring: HBM is bounded
+        by the budget plus the ring plus one model. Pass 0 (``coef = 0``, nothing stored) gives the K
+        squared distances to the global model; passes 1 .. ``iterations`` take ``coef =
+        clip_coefficients(d, tau)`` of the pass before, move the centre IN PLACE — slice by slice where
+        updates sit on the host, through the same ring as :meth:`result` — and give the distances to the
+        new point (``ops.centered_clip_step``, kernel ``k_cclip_dist``). Only the last pass is followed
+        by the centre's copy to the host; ``iterations = 0`` returns the converted centre.
+
+        A client whose distance to the global model is not finite (an ``inf`` or a NaN in its update) is
+        excluded: its coefficient is 0 in every pass. ``ValueError`` when that is every client — which a
+        non-finite global model also causes — or when a later distance of a remaining client turns
+        non-finite.
+
+        Kept on the pipeline: ``coefficients`` (the last pass's), ``distances`` (sqrt of the last pass's
+        d), ``excluded`` (FIFO indices) and ``trace`` (one ``(coef, d)`` pair per pass, float64)."""
+        K = len(self.updates)
+        if not 1 <= K <= ops.MAX_ORDER_K:
+            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        if iterations < 0 or not (tau > 0 and np.isfinite(tau)):
+            raise ValueError(f"iterations={iterations}, tau={tau}")
+        L = int(iterations)
+        self.coefficients, self.distances, self.excluded, self.trace = None, None, [], []
+        packed = self._pack_center(center_arrays)
+        out = [None] * len(self.layout.shapes)
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
+                cen = {}
+                for dt, host in packed.items():      # allocated on the stream that writes and reads it
+                    cen[dt] = torch.empty(host.numel(), dtype=host.dtype, device=self.device)
+                    cen[dt].copy_(host, non_blocking=True)
+                for u in self.updates:
+                    if isinstance(u, StagedModel):
+                        self.compute.wait_event(u.ready)
+                coef = np.zeros(K, dtype=np.float64)
+                d = self._clip_pass(coef, cen, False)
+                good = np.isfinite(d)
+                self.excluded = [k for k in range(K) if not good[k]]
+                if not good.any():
+                    raise ValueError(f"no client has a finite distance to the global model: {d}")
+                for _ in range(L):
+                    coef = clip_coefficients(d, tau)
+                    d = self._clip_pass(coef, cen, True)
+                    if not np.isfinite(d[good]).all():
+                        raise ValueError(f"a distance turned non-finite after a clipping step: {d}")
+                tic = time.perf_counter()
+                for dt, host in packed.items():
+                    host.copy_(cen[dt], non_blocking=True)
+                self.compute.synchronize()
+                self.time_d2h += time.perf_counter() - tic
+        except BaseException:
+            torch.cuda.synchronize(self.device)
+            raise
+        self.coefficients = coef
+        with np.errstate(invalid="ignore"):
+            self.distances = np.sqrt(d)
+        for dt in self.layout.groups:
+            self.layout.unpack_group(packed[dt].numpy(), dt, out, copy=False)
+        return out
+
+    def _pack_center(self, center_arrays):
+        """The centre's dtype groups as pinned host tensors of ``ops.order_mean_dtype``, after the layout
+        check: the round's shapes, each tensor of the updates' dtype or of that output dtype."""
+        arrays = [np.asarray(a) for a in center_arrays]
+        if len(arrays) != len(self.layout.shapes):
+            raise ValueError(f"the global model has {len(arrays)} tensors, the round's updates {len(self.layout.shapes)}")
+        for i, a in enumerate(arrays):
+            if tuple(a.shape) != tuple(self.layout.shapes[i]):
+                raise ValueError(f"tensor {i} of the global model has shape {a.shape}, the round's {self.layout.shapes[i]}")
+        packed = {}
+        for dt in self.layout.groups:
+            odt = self._out_dt[dt]
+            onp = ops.numpy_dtype(odt)
+            host = packed[dt] = torch.empty(self.layout.group_elems[dt], dtype=odt, pin_memory=True)
+            flat = host.numpy()
+            for i, off in self.layout.members[dt]:
+                a = arrays[i]
+                if a.dtype != dt and a.dtype != onp:
+                    raise ValueError(f"tensor {i} of the global model is {a.dtype}, the round's updates are {dt} "
+                                     f"(a global model of {onp} is taken too)")
+                flat[off:off + a.size] = a.reshape(-1)         # (dt -> its output dtype is exact)
+        return packed
+
+    def _clip_pass(self, coef, cen, store):
+        """One fused pass over every dtype group with the coefficients ``coef``: the K squared distances to
+        the new point as a float64 host array; with ``store`` the centre ``cen`` (device tensors by dtype
+        group) is moved in place. Appends ``(coef, d)`` to ``trace``."""
+        K = len(self.updates)
+        coef = np.array(coef, dtype=np.float64)
+        dist = torch.zeros(K, dtype=torch.float64, device=self.device)
+        state = [False]                              # dist is written by the pass's first launch, added to after
+        for dt in self.layout.groups:
+            if self.layout.group_elems[dt] == 0:
+                continue
+            c = cen[dt]
+
+            def launch(b, lo, hi, views, step, c=c):
+                v = c[lo:hi]
+                ops.centered_clip_step(views, v, coef, out=v if store else None, dist=dist, accumulate=state[0],
+                                       store=store, stream=self.compute)
+                state[0] = True
+
+            self._walk_group(dt, None, launch, None)
+        tic = time.perf_counter()
+        d = dist.cpu().numpy()                       # (synchronises the compute stream)
+        self.time_d2h += time.perf_counter() - tic
+        self.trace.append((coef, d))
+        return d
 
     def _host_flat(self, arrays, dt):
         """(flat array, element offset in the group) of the non-empty members of group ``dt``."""

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 11
+#define FA_ABI_VERSION 12
 
 /* element type codes */
 enum fa_dtype {
@@ -438,6 +438,48 @@ int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int
 int64_t fa_wmean_sqdist_work(int K, int64_t P);
 int fa_weighted_mean_sqdist(void* out, int out_dtype, double* dist, const void* const* updates, int upd_dtype,
                             const double* beta, int K, int64_t P, int accumulate, double* work, void* stream);
+
+/*
+ * fa_centered_clip_step (ABI 12): one step of centred clipping (Karimireddy, He and Jaggi, "Learning from
+ * History for Byzantine Robust Optimization") — the centre v moved by the clipped differences of K client
+ * updates to it — and the K squared distances of the updates to the NEW point, in ONE pass over the
+ * updates. With C and the output type O of upd_dtype as for fa_weighted_mean_sqdist (O -> C is exact) and
+ * c_k = C(coef[k]) (each cast once), per element
+ *     acc = C(v),   then over the clients with c_k != 0 in index order:   acc = acc + c_k (C(u_k) - C(v)),
+ *     v' = acc rounded once to O,
+ * the difference, the product and the add each rounded once in C (no FMA, no reassociation): a client
+ * equal to the centre contributes exactly 0, a client with c_k = 0 is no part of v' (its inf or NaN cannot
+ * reach it). Every c_k = 0 is legal: v' = O(C(v)), and with out = NULL the call is the distances-only pass
+ * that starts the rule. Then, for EVERY k,
+ *     dist[k] = sum_p (C(u_k[p]) - C(v'[p]))^2       with v' as stored (or as it would be, out = NULL),
+ * by fa_weighted_mean_sqdist's arithmetic and within its error bound. The caller clips:
+ * coef[k] = min(1, tau / sqrt(d_k)) / K_good from the distances of the step before.
+ *
+ * Deterministic as fa_weighted_mean_sqdist: tiles, chains and partials depend only on (K, P, upd_dtype),
+ * the grid cap is a constant, no floating-point atomic; the same bits on every call and at every pointer
+ * alignment.
+ *
+ * out      DEVICE buffer of P elements of out_dtype; NULL: v' is computed but not stored; `center` itself:
+ *          the step is taken in place (safe by construction: a workgroup reads its tile of the centre
+ *          before it stores to it, and tiles are disjoint); any other buffer must not overlap `center`
+ * center   DEVICE buffer of P elements of out_dtype
+ * out_dtype  F32 for F32 / BF16 updates, F16 for F16, F64 for F64 / I32 / I64
+ * dist     DEVICE buffer of K doubles
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * coef     HOST array of K doubles, each finite and >= 0 (in C too)
+ * accumulate  0: dist is written; 1: the call's distances are added to it in f64 (dtype groups, slices)
+ * work     DEVICE scratch of fa_centered_clip_work(K, P) doubles (>= 1; enough for every dtype)
+ * FA_EINVAL: a null dist, center, coef, updates or work, a null entry of updates when P > 0, K outside
+ * 1..64, P < 0, a coef that is negative or not finite (also as a C value), out overlapping center without
+ * being equal to it; FA_EDTYPE: a dtype outside the six or an out_dtype that is not the table's — all
+ * before any HIP call. P = 0 is FA_OK: with accumulate = 0 the K zeros are still written, with
+ * accumulate = 1 nothing is launched. A non-finite input value is not an error. fa_last_kernel reports
+ * "k_cclip_dist".
+ */
+int64_t fa_centered_clip_work(int K, int64_t P);
+int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* dist, const void* const* updates,
+                          int upd_dtype, const double* coef, int K, int64_t P, int accumulate, double* work,
+                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,9 @@ int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chai
  * status codes.                                                                                      */
 int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
                              int* flush_tiles);
+/* And for fa_centered_clip_step, whose tile holds one more column (the centre's). Same status codes. */
+int fa_centered_clip_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                              int* flush_tiles);
 
 /* The knobs of fa_tune (process-global; measurement and tuning only). Every setting computes the
  * reference's bits except OPT_MIX and OPT_WIN_PERIOD > 0 without OPT_WIN_PROD, which run access-
