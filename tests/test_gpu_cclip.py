@@ -12,6 +12,9 @@ import torch
 
 import cclip_ref as cr
 from golden_io import assert_lists_identical
+from robust_checks import check_cclip_chain as _check_chain
+from robust_checks import nan_clients as _nan_clients
+from robust_checks import same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -84,17 +87,6 @@ def _coef(rng, K):
     if K > 1:
         coef[int(rng.integers(0, K))] = 0.0
     return coef.tolist()
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(f"u{a.dtype.itemsize}")
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    diff = _bits(got) != _bits(want)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} values differ, first at {int(np.argmax(diff))}"
 
 
 def _check_d(got, want, rtol, what):
@@ -525,10 +517,6 @@ def _tau(spec):
     return 0.3 * math.sqrt(sum(int(np.prod(s)) for s, _ in spec))
 
 
-def _nan_clients(ups):
-    return [k for k, u in enumerate(ups) if any(np.dtype(a.dtype).kind == "f" and not np.isfinite(a).all() for a in u)]
-
-
 def _run_round(ups, center, staged, parameters, budget=None, agg=None, uh=None):
     from fedn_amd.aggregators import get_aggregator
     from fedn_amd.ingest import StagingUpdateHandler
@@ -546,45 +534,6 @@ def _run_round(ups, center, staged, parameters, budget=None, agg=None, uh=None):
         if st is not None:
             st.close()
     return model, data, uh, mus, agg, gid
-
-
-def _rtol_of(ups):
-    from fedn_amd import ops
-    return max(ops.sqdist_rtol(np.asarray(a).dtype, np.asarray(a).size) for a in ups[0])
-
-
-def _check_chain(ups, center, agg, model, iterations, tau, what):
-    """The rule's chain, pass by pass, from the pipeline's own trace: (a) coef_0 is all zeros; (b) every
-    d_t is within the bound of the oracle's distances to the replayed v_t, non-finite exactly for the NaN
-    clients; (c) coef_t+1 is the host rule of d_t, bit for bit; (d) the model is the oracle's chain
-    v_0 -> ... -> v_L replayed with the device's coefficients, bit for bit."""
-    K = len(ups)
-    trace = agg.trace
-    assert len(trace) == iterations + 1, f"{what}: {len(trace)} passes for {iterations} iterations"
-    want_excluded = _nan_clients(ups)
-    assert agg.excluded == want_excluded, f"{what}: excluded {agg.excluded}, the NaN clients are {want_excluded}"
-    _same_bits(np.asarray(trace[0][0]), np.zeros(K), f"{what}: (a) coef_0")
-    rtol = _rtol_of(ups)
-    v = cr.model_center(ups, center)
-    for t, (coef, d) in enumerate(trace):
-        assert coef.dtype == np.float64 and d.dtype == np.float64 and coef.shape == d.shape == (K,)
-        if t:
-            v = cr.model_step(ups, v, coef)
-        want = cr.model_dists(ups, v)
-        fin = np.isfinite(want)
-        assert np.array_equal(np.isfinite(d), fin), f"{what}: (b) pass {t}: non-finite entries {d} vs {want}"
-        assert sorted(np.flatnonzero(~fin).tolist()) == want_excluded
-        err = np.abs(d[fin] - want[fin])
-        worst = float((err / np.where(want[fin] > 0, want[fin], 1.0)).max())
-        print(f"{what}: pass {t}: worst relative error {worst:.3e} (bound {rtol:.3e})")
-        assert (err <= rtol * want[fin]).all(), f"{what}: (b) pass {t}"
-        if t + 1 < len(trace):
-            _same_bits(np.asarray(trace[t + 1][0]), np.array(cr.coefficients(d, tau)), f"{what}: (c) coef_{t + 1}")
-    _same_bits(np.asarray(agg.coefficients), np.asarray(trace[-1][0]), f"{what}: coefficients")
-    with np.errstate(invalid="ignore"):
-        _same_bits(np.asarray(agg.distances), np.sqrt(trace[-1][1]), f"{what}: distances")
-    assert all(c[k] == 0 for c, _ in trace for k in want_excluded)
-    assert_lists_identical(model, v, f"{what}: (d) model")
 
 
 def _flat64(model):

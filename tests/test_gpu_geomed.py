@@ -11,6 +11,9 @@ import torch
 
 import geomed_ref as gr
 from golden_io import assert_lists_identical
+from robust_checks import check_geomed_chain as _check_chain
+from robust_checks import nan_clients as _nan_clients
+from robust_checks import same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -72,17 +75,6 @@ def _beta(rng, K):
     if K > 1:
         beta[int(rng.integers(0, K))] = 0.0
     return beta.tolist()
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(f"u{a.dtype.itemsize}")
-
-
-def _same_bits(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    diff = _bits(got) != _bits(want)
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} values differ, first at {int(np.argmax(diff))}"
 
 
 def _check_d(got, want, rtol, what):
@@ -436,10 +428,6 @@ def _round_updates(seed, K, spec, fraction=FRACTION):
     return ups, hostile
 
 
-def _nan_clients(ups):
-    return [k for k, u in enumerate(ups) if any(np.dtype(a.dtype).kind == "f" and not np.isfinite(a).all() for a in u)]
-
-
 def _run_round(ups, staged, parameters=None, budget=None, agg=None, uh=None):
     from fedn_amd.aggregators import get_aggregator
     from fedn_amd.ingest import StagingUpdateHandler
@@ -456,45 +444,6 @@ def _run_round(ups, staged, parameters=None, budget=None, agg=None, uh=None):
         if st is not None:
             st.close()
     return model, data, uh, mus, agg
-
-
-def _rtol_of(ups):
-    from fedn_amd import ops
-    return max(ops.sqdist_rtol(np.asarray(a).dtype, np.asarray(a).size) for a in ups[0])
-
-
-def _check_chain(ups, agg, model, iterations, nu, what):
-    """The Weiszfeld chain, pass by pass, from the pipeline's own trace: (a) beta_0 is 1/K_good with zeros
-    on the excluded clients; (b) every d_t is within the bound of the oracle's distances to the oracle's
-    mean at beta_t, non-finite where the oracle's are; (c) beta_t+1 is the host rule of d_t, bit for bit;
-    (d) the model is the oracle's mean at the last beta, bit for bit."""
-    K = len(ups)
-    T = 0 if K == 1 else iterations
-    trace = agg.trace
-    assert len(trace) == T + 1, f"{what}: {len(trace)} passes for {iterations} iterations"
-    want_excluded = _nan_clients(ups)
-    assert agg.excluded == want_excluded, f"{what}: excluded {agg.excluded}, the NaN clients are {want_excluded}"
-    beta0 = np.full(K, 1.0 / (K - len(want_excluded)))
-    beta0[want_excluded] = 0.0
-    _same_bits(np.asarray(trace[0][0]), beta0, f"{what}: (a) beta_0")
-    rtol = _rtol_of(ups)
-    for t, (beta, d) in enumerate(trace):
-        assert beta.dtype == np.float64 and d.dtype == np.float64 and beta.shape == d.shape == (K,)
-        want = gr.model_dists(ups, beta)
-        fin = np.isfinite(want)
-        assert np.array_equal(np.isfinite(d), fin), f"{what}: (b) pass {t}: non-finite entries {d} vs {want}"
-        assert sorted(np.flatnonzero(~fin).tolist()) == want_excluded
-        err = np.abs(d[fin] - want[fin])
-        worst = float((err / np.where(want[fin] > 0, want[fin], 1.0)).max())
-        print(f"{what}: pass {t}: worst relative error {worst:.3e} (bound {rtol:.3e})")
-        assert (err <= rtol * want[fin]).all(), f"{what}: (b) pass {t}"
-        if t + 1 < len(trace):
-            _same_bits(np.asarray(trace[t + 1][0]), np.array(gr.weights(d, nu)), f"{what}: (c) beta_{t + 1}")
-    _same_bits(np.asarray(agg.weights), np.asarray(trace[-1][0]), f"{what}: weights")
-    with np.errstate(invalid="ignore"):
-        _same_bits(np.asarray(agg.distances), np.sqrt(trace[-1][1]), f"{what}: distances")
-    assert all(agg.weights[k] == 0 for k in want_excluded)
-    assert_lists_identical(model, gr.model_wmean(ups, trace[-1][0]), f"{what}: (d) model")
 
 
 def _flat64(model):

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+from late_streams import side_by_side_streams as _side_by_side_streams
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -42,31 +44,6 @@ def _busy(stream, ms_ish=40):
     for _ in range(ms_ish):
         ops.fedavg_fold(agg, ups, [1] * 8, list(range(1, 9)), init=True, stream=stream)
     return ups, agg
-
-
-def _side_by_side_streams():
-    """(staging, compute): two streams of the device that run side by side. torch hands streams out of
-    a pool and the runtime maps them onto a few hardware queues; two streams on one queue run in
-    order, so the poison (staging stream) would wait behind the busy compute stream and land after
-    the read, and the test would say nothing about the knob. Which pooled streams share a queue
-    depends on how many streams the process drew before and in which order they were first used,
-    so the pair is chosen by looking: a stream whose small fill ends while the other still spins."""
-    compute = torch.cuda.Stream(DEV)
-    for _ in range(16):
-        staging = torch.cuda.Stream(DEV)
-        spun, filled = torch.cuda.Event(), torch.cuda.Event()
-        with torch.cuda.stream(compute):
-            torch.cuda._sleep(30_000_000)                  # ~10 ms or more
-            spun.record(compute)
-        with torch.cuda.stream(staging):
-            torch.zeros(16, device=DEV)
-            filled.record(staging)
-        filled.synchronize()
-        apart = not spun.query()
-        compute.synchronize()
-        if apart:
-            return staging, compute
-    pytest.fail("no stream of the pool runs side by side with the compute stream")
 
 
 @pytest.mark.parametrize("protect", ["none", "hold", "record_stream"])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from late_streams import busy_then_zero_fills as _busy_then_zero_fills
 from oracle import numpy_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -28,24 +29,6 @@ def _gpu():
     torch.cuda.empty_cache()             # no other free block of the sizes below in the pool
     yield
     torch.cuda.synchronize()
-
-
-def _busy_then_zero_fills(nbytes, count=16, folds=200):
-    """Queue ~tens of ms of folds on the current stream, then ``count`` blocks of ``nbytes`` (an int or
-    a list of sizes, ``count`` of each) zero-filled behind them, and free the blocks (their fills still
-    queued)."""
-    from fedn_amd import ops
-    P = 50_000_000
-    ups = [torch.ones(P, device=DEV) for _ in range(8)]
-    agg = torch.empty(P, device=DEV)
-    for _ in range(folds):
-        ops.fedavg_fold(agg, ups, [1] * 8, list(range(1, 9)), init=True)
-    sizes = nbytes if isinstance(nbytes, (list, tuple)) else [nbytes]
-    blocks = [torch.empty(nb, dtype=torch.uint8, device=DEV) for nb in sizes for _ in range(count)]
-    for b in blocks:
-        b.zero_()
-    del blocks
-    return ups, agg                      # kept until the test ends: their folds are still queued too
 
 
 def _same(got, want, what):
