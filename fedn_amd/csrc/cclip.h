@@ -2,8 +2,11 @@
 // it, and the K squared distances to the new point, in one pass (fa_centered_clip_step, kernel k_cclip_dist).
 //
 // Included by fedagg.hip inside its anonymous namespace, after wmean_dist.h: it is that file's kernel
-// "with one extra client" and uses its tile constants, traits, conversions and k_wmean_finish. With C the
-// compute type and O the output type of the dtype family (WmTraits) and c_k = C(coef[k]):
+// "with one extra client". This file holds the kernel and its launcher alone; from wmean_dist.h it takes the
+// tile constants (kWm*), wm_kp / wm_ck / wm_waves, WmTraits, WmTable, wm_out / wm_back, and the whole host
+// side: WmGeom and wm_geom at K + 1 tile columns, wm_workgroups, wm_fill_table, wm_for_kp and wm_finish
+// (k_wmean_finish). With C the compute type and O the output type of the dtype family (WmTraits) and
+// c_k = C(coef[k]):
 //     v'[p] = O((C(v[p]) + c_a (C(u_a[p]) - C(v[p]))) + c_b (C(u_b[p]) - C(v[p])) + ...)
 //                                                         over the clients with c_k != 0, in index order,
 //     d[k]  = sum_p (C(u_k[p]) - C(v'[p]))^2               for every k,
@@ -20,32 +23,13 @@
 // steps, so out may be the centre itself. Nothing depends on timing, on the device or on a pointer's
 // alignment.
 
-struct CcGeom {
-    int TE, KS, FT, GRID;   // as WmGeom
-};
-
-inline CcGeom cc_geom(int K, int csize, int waves) {
-    CcGeom g;
-    const int KP = wm_kp(K);
-    g.KS = (K + 1) | 1;
-    const int te = kWmTileBytes / (g.KS * csize);
-    g.TE = (te < kWmTileMax ? te : kWmTileMax) / 8 * 8;
-    const int sl = kBlock / (KP / wm_ck(KP));          // elements the lanes cover at a time
-    g.FT = kWmChain / ((g.TE + sl - 1) / sl);
-    g.GRID = 256 * waves;
-    return g;
-}
-
-// waves a SIMD the registers are held to (DESIGN.md §3.10's table), and so the grid cap: k_wmean_dist's
-template <typename T> constexpr int cc_waves(int KP) { return wm_waves<T>(KP); }
-
 __device__ __forceinline__ float cc_center(float v, float) { return v; }
 __device__ __forceinline__ float cc_center(f16 v, float) { return f16_to_f32(v.bits); }
 __device__ __forceinline__ double cc_center(double v, double) { return v; }
 
 // `live`: bit k set for every client with a nonzero coefficient
 template <typename T, int KP, int CK>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(cc_waves<T>(KP), cc_waves<T>(KP))))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(wm_waves<T>(KP), wm_waves<T>(KP))))
 k_cclip_dist(typename WmTraits<T>::O* out, const typename WmTraits<T>::O* center, double* __restrict__ work,
              const WmTable<typename WmTraits<T>::C> tab, const int K, const unsigned long long live, const int64_t P,
              const int TE, const int KS, const int flush_tiles, const int vec, const int cvec) {
@@ -206,57 +190,23 @@ k_cclip_dist(typename WmTraits<T>::O* out, const typename WmTraits<T>::O* center
     if (t < K) work[(int64_t)blockIdx.x * kMaxK + t] = part64[t];
 }
 
-// the geometry of (dtype, K); dtype is one of the six
-inline CcGeom cc_geom_dt(int dtype, int K) {
-    const int KP = wm_kp(K);
-    switch (dtype) {
-        case FA_F32: return cc_geom(K, 4, cc_waves<float>(KP));
-        case FA_F16: return cc_geom(K, 4, cc_waves<f16>(KP));
-        case FA_BF16: return cc_geom(K, 4, cc_waves<bf16>(KP));
-        case FA_F64: return cc_geom(K, 8, cc_waves<double>(KP));
-        case FA_I32: return cc_geom(K, 8, cc_waves<int32_t>(KP));
-        default: return cc_geom(K, 8, cc_waves<int64_t>(KP));
-    }
-}
-
-inline int64_t cc_workgroups(int64_t P, const CcGeom& gm) {
-    return std::min<int64_t>((P + gm.TE - 1) / gm.TE, gm.GRID);
-}
-
-template <typename T, int KP>
-void launch_cclip_dist_kp(void* out, const void* center, double* work, const WmTable<typename WmTraits<T>::C>& tab, int K,
-                          unsigned long long live, int64_t P, const CcGeom& gm, int nwg, bool vec, bool cvec,
-                          hipStream_t st) {
-    using O = typename WmTraits<T>::O;
-    hipLaunchKernelGGL((k_cclip_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st, static_cast<O*>(out),
-                       static_cast<const O*>(center), work, tab, K, live, P, gm.TE, gm.KS, gm.FT, (int)vec, (int)cvec);
-}
-
 template <typename T>
 int launch_cclip_dist(void* out, const void* center, double* dist, const void* const* ups, const double* cc, int K,
                       int64_t P, int accumulate, double* work, hipStream_t st) {
     using C = typename WmTraits<T>::C;
+    using O = typename WmTraits<T>::O;
     WmTable<C> tab;
-    bool vec = true;
-    unsigned long long live = 0;
-    for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
-        tab.b[k] = k < K ? (C)cc[k] : C(0);            // (exact: cc[k] is C(coef[k]) held in a double)
-        if (k < K) vec = vec && aligned16(ups[k]);
-        if (k < K && cc[k] != 0.0) live |= 1ull << k;
-    }
-    const CcGeom gm = cc_geom(K, (int)sizeof(C), cc_waves<T>(wm_kp(K)));
-    const int nwg = (int)cc_workgroups(P, gm);
+    const WmLive tl = wm_fill_table(tab, ups, cc, K, false);
+    const WmGeom gm = wm_geom(K, (int)sizeof(C), wm_waves<T>(wm_kp(K)), K + 1);
+    const int nwg = (int)wm_workgroups(P, gm);
     const bool cvec = aligned16(center);
     g_kernel = "k_cclip_dist";
-    if (nwg > 0) {
-        switch (wm_kp(K)) {
-            case 8: launch_cclip_dist_kp<T, 8>(out, center, work, tab, K, live, P, gm, nwg, vec, cvec, st); break;
-            case 16: launch_cclip_dist_kp<T, 16>(out, center, work, tab, K, live, P, gm, nwg, vec, cvec, st); break;
-            case 32: launch_cclip_dist_kp<T, 32>(out, center, work, tab, K, live, P, gm, nwg, vec, cvec, st); break;
-            default: launch_cclip_dist_kp<T, 64>(out, center, work, tab, K, live, P, gm, nwg, vec, cvec, st); break;
-        }
-    }
-    hipLaunchKernelGGL(k_wmean_finish, dim3(1), dim3(kMaxK), 0, st, dist, work, K, nwg, accumulate);
-    return check_launch("fa_centered_clip_step: kernel launch");
+    if (nwg > 0)
+        wm_for_kp(K, [&](auto kp) {
+            constexpr int KP = decltype(kp)::value;
+            hipLaunchKernelGGL((k_cclip_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st,
+                               static_cast<O*>(out), static_cast<const O*>(center), work, tab, K, tl.live, P, gm.TE, gm.KS,
+                               gm.FT, (int)tl.vec, (int)cvec);
+        });
+    return wm_finish(dist, work, K, nwg, accumulate, st, "fa_centered_clip_step: kernel launch");
 }

@@ -706,14 +706,7 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
         return fail(FA_EDTYPE, "fa_trimmed_mean: unsupported dtype pair (update %d, output %d)", upd_dtype, out_dtype);
     if (P == 0) return FA_OK;
     if (const int rc = check_updates("fa_trimmed_mean", updates, K)) return rc;
-    switch (upd_dtype) {
-        case FA_F32: return launch_order_mean<float>(out, updates, K, trim, P, st);
-        case FA_F64: return launch_order_mean<double>(out, updates, K, trim, P, st);
-        case FA_F16: return launch_order_mean<f16>(out, updates, K, trim, P, st);
-        case FA_BF16: return launch_order_mean<bf16>(out, updates, K, trim, P, st);
-        case FA_I32: return launch_order_mean<int32_t>(out, updates, K, trim, P, st);
-        default: return launch_order_mean<int64_t>(out, updates, K, trim, P, st);
-    }
+    return for_dtype(upd_dtype, [&](auto t) { return launch_order_mean<decltype(t)>(out, updates, K, trim, P, st); });
 }
 
 
@@ -748,93 +741,55 @@ int fa_pairwise_sqdist(double* D, const void* const* updates, int upd_dtype, int
 int64_t fa_wmean_sqdist_work(int K, int64_t P) {
     if (K < 1 || K > kMaxK || P < 0) return 0;
     // f64 updates: the smallest tile and the largest grid, so the most workgroups; kMaxK doubles per workgroup
-    return std::max<int64_t>(wm_workgroups(P, wm_geom_dt(FA_F64, K)) * kMaxK, 1);
+    return std::max<int64_t>(wm_workgroups(P, wm_geom_dt(FA_F64, K, K)) * kMaxK, 1);
 }
 
 int fa_weighted_mean_sqdist(void* out, int out_dtype, double* dist, const void* const* updates, int upd_dtype,
                             const double* beta, int K, int64_t P, int accumulate, double* work, void* stream) {
     g_err[0] = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!dist || !beta || !updates || !work) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: null pointer argument");
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: K=%d outside 1..%d", K, kMaxK);
-    if (P < 0) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: negative size (P=%lld)", (long long)P);
-    const bool f32fam = pair_family(upd_dtype) == 32;
-    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "fa_weighted_mean_sqdist: unsupported dtype %d", upd_dtype);
-    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
-    if (out_dtype != want)
-        return fail(FA_EDTYPE, "fa_weighted_mean_sqdist: updates of dtype %d give a mean of dtype %d, not %d", upd_dtype,
-                    want, out_dtype);
     double bc[kMaxK];
-    int kfirst = -1;
-    for (int k = 0; k < K; ++k) {
-        if (!(beta[k] >= 0.0) || std::isinf(beta[k]))
-            return fail(FA_EINVAL, "fa_weighted_mean_sqdist: beta[%d]=%g is negative or not finite", k, beta[k]);
-        bc[k] = f32fam ? (double)(float)beta[k] : beta[k];       // C(beta[k]), cast once
-        if (std::isinf(bc[k]))
-            return fail(FA_EINVAL, "fa_weighted_mean_sqdist: beta[%d]=%g is not finite in the compute type", k, beta[k]);
-        if (bc[k] != 0.0 && kfirst < 0) kfirst = k;
-    }
-    if (kfirst < 0) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: every weight is zero in the compute type");
+    if (const int rc = wm_check_step("fa_weighted_mean_sqdist", "beta", "give a mean", dist && beta && updates && work,
+                                     out_dtype, upd_dtype, beta, K, P, bc))
+        return rc;
+    int kfirst = 0;
+    while (kfirst < K && bc[kfirst] == 0.0) ++kfirst;
+    if (kfirst == K) return fail(FA_EINVAL, "fa_weighted_mean_sqdist: every weight is zero in the compute type");
     if (P > 0)                                               // (an empty buffer may be a null pointer)
         if (const int rc = check_updates("fa_weighted_mean_sqdist", updates, K)) return rc;
     if (accumulate && P == 0) return FA_OK;                  // nothing to add: no launch
-    switch (upd_dtype) {
-        case FA_F32: return launch_wmean_dist<float>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-        case FA_F16: return launch_wmean_dist<f16>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-        case FA_BF16: return launch_wmean_dist<bf16>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-        case FA_F64: return launch_wmean_dist<double>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-        case FA_I32: return launch_wmean_dist<int32_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-        default: return launch_wmean_dist<int64_t>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
-    }
+    return for_dtype(upd_dtype, [&](auto t) {
+        return launch_wmean_dist<decltype(t)>(out, dist, updates, bc, kfirst, K, P, accumulate, work, st);
+    });
 }
 
 int64_t fa_centered_clip_work(int K, int64_t P) {
     if (K < 1 || K > kMaxK || P < 0) return 0;
-    // the dtype with the most workgroups (the smallest tile, the largest grid); kMaxK doubles per workgroup
-    int64_t n = 0;
-    for (const int dt : {FA_F32, FA_F16, FA_BF16, FA_F64, FA_I32, FA_I64}) n = std::max(n, cc_workgroups(P, cc_geom_dt(dt, K)));
-    return std::max<int64_t>(n * kMaxK, 1);
+    // f64 updates again: of the six dtypes they have the smallest tile (8-byte values) and the largest grid
+    // (four waves a SIMD at every K), so no other dtype has more workgroups at any (K, P)
+    return std::max<int64_t>(wm_workgroups(P, wm_geom_dt(FA_F64, K, K + 1)) * kMaxK, 1);
 }
 
 int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* dist, const void* const* updates,
                           int upd_dtype, const double* coef, int K, int64_t P, int accumulate, double* work, void* stream) {
     g_err[0] = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!dist || !center || !coef || !updates || !work)
-        return fail(FA_EINVAL, "fa_centered_clip_step: null pointer argument");
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_centered_clip_step: K=%d outside 1..%d", K, kMaxK);
-    if (P < 0) return fail(FA_EINVAL, "fa_centered_clip_step: negative size (P=%lld)", (long long)P);
-    const bool f32fam = pair_family(upd_dtype) == 32;
-    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "fa_centered_clip_step: unsupported dtype %d", upd_dtype);
-    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
-    if (out_dtype != want)
-        return fail(FA_EDTYPE, "fa_centered_clip_step: updates of dtype %d move a centre of dtype %d, not %d", upd_dtype,
-                    want, out_dtype);
     double cc[kMaxK];
-    for (int k = 0; k < K; ++k) {
-        if (!(coef[k] >= 0.0) || std::isinf(coef[k]))
-            return fail(FA_EINVAL, "fa_centered_clip_step: coef[%d]=%g is negative or not finite", k, coef[k]);
-        cc[k] = f32fam ? (double)(float)coef[k] : coef[k];       // C(coef[k]), cast once
-        if (std::isinf(cc[k]))
-            return fail(FA_EINVAL, "fa_centered_clip_step: coef[%d]=%g is not finite in the compute type", k, coef[k]);
-    }
+    if (const int rc = wm_check_step("fa_centered_clip_step", "coef", "move a centre",
+                                     dist && center && coef && updates && work, out_dtype, upd_dtype, coef, K, P, cc))
+        return rc;
     if (out && out != center && P > 0) {                     // in place or disjoint, nothing between
         const uintptr_t a = reinterpret_cast<uintptr_t>(out), b = reinterpret_cast<uintptr_t>(center);
-        const uintptr_t len = (uintptr_t)P * dt_size(want);
+        const uintptr_t len = (uintptr_t)P * dt_size(out_dtype);
         if (a < b + len && b < a + len)
             return fail(FA_EINVAL, "fa_centered_clip_step: out and center overlap without being the same buffer");
     }
     if (P > 0)                                               // (an empty buffer may be a null pointer)
         if (const int rc = check_updates("fa_centered_clip_step", updates, K)) return rc;
     if (accumulate && P == 0) return FA_OK;                  // nothing to add: no launch
-    switch (upd_dtype) {
-        case FA_F32: return launch_cclip_dist<float>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-        case FA_F16: return launch_cclip_dist<f16>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-        case FA_BF16: return launch_cclip_dist<bf16>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-        case FA_F64: return launch_cclip_dist<double>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-        case FA_I32: return launch_cclip_dist<int32_t>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-        default: return launch_cclip_dist<int64_t>(out, center, dist, updates, cc, K, P, accumulate, work, st);
-    }
+    return for_dtype(upd_dtype, [&](auto t) {
+        return launch_cclip_dist<decltype(t)>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+    });
 }
 
 #ifdef FEDAGG_PROBES

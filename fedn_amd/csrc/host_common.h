@@ -1,6 +1,6 @@
 // host_common.h — host code that more than one kernel family's launch path uses: filling a launch's
-// client table, the device's size (CUs, resident workgroups of a kernel), and the argument checks and
-// device mappings that several entry points share.
+// client table, the device's size (CUs, resident workgroups of a kernel), the robust entry points' dispatch
+// by update dtype, and the argument checks and device mappings that several entry points share.
 //
 // Included by fedagg.hip inside its anonymous namespace, after the kernel headers and probes.h: it uses
 // ClientTable (fold_rules.h), the cfg_* getters (probes.h) and that file's error plumbing.
@@ -66,6 +66,19 @@ int resident_blocks() {
         blocks_per_cu.store(nb, std::memory_order_relaxed);
     }
     return nb;
+}
+
+// f(T{}) with the element type T of `dtype`, one of the six the robust kernels take (the caller has checked it)
+template <typename F>
+auto for_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case FA_F32: return f(float{});
+        case FA_F16: return f(f16{});
+        case FA_BF16: return f(bf16{});
+        case FA_F64: return f(double{});
+        case FA_I32: return f(int32_t{});
+        default: return f(int64_t{});
+    }
 }
 
 // the first null among a round's K update pointers, reported in `who`'s name

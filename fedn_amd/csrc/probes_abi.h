@@ -3,7 +3,7 @@
 //
 // Included by fedagg.hip inside its extern "C" block, in the probe build alone. It uses g_cfg and the
 // probe kernels (probes.h), launch_fedavg_pipe (fedavg_launch.h), fill_table (host_common.h) and the
-// geometry tables of pair_dist.h, wmean_dist.h and cclip.h. DESIGN.md §3.5 describes the stream probes.
+// geometry tables of pair_dist.h and wmean_dist.h (cclip.h's kernel uses the latter's). DESIGN.md §3.5 describes the stream probes.
 
 int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
                                 int* flush_tiles) {
@@ -25,12 +25,13 @@ int fa_pairwise_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chai
     return FA_OK;
 }
 
-int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
-                             int* flush_tiles) {
+// the two fused-pass kernels' geometry at `cols` tile columns, in `who`'s name
+static int wm_geometry(const char* who, int upd_dtype, int K, int cols, int* tile_elems, int* chain_terms,
+                       int* max_workgroups, int* flush_tiles) {
     g_err[0] = 0;
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_wmean_sqdist_geometry: K=%d outside 1..%d", K, kMaxK);
-    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "fa_wmean_sqdist_geometry: unsupported dtype %d", upd_dtype);
-    const WmGeom gm = wm_geom_dt(upd_dtype, K);
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "%s: K=%d outside 1..%d", who, K, kMaxK);
+    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "%s: unsupported dtype %d", who, upd_dtype);
+    const WmGeom gm = wm_geom_dt(upd_dtype, K, cols);
     if (tile_elems) *tile_elems = gm.TE;
     if (chain_terms) *chain_terms = kWmChain;
     if (max_workgroups) *max_workgroups = gm.GRID;
@@ -38,17 +39,15 @@ int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_t
     return FA_OK;
 }
 
+int fa_wmean_sqdist_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
+                             int* flush_tiles) {
+    return wm_geometry("fa_wmean_sqdist_geometry", upd_dtype, K, K, tile_elems, chain_terms, max_workgroups, flush_tiles);
+}
+
 int fa_centered_clip_geometry(int upd_dtype, int K, int* tile_elems, int* chain_terms, int* max_workgroups,
                               int* flush_tiles) {
-    g_err[0] = 0;
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_centered_clip_geometry: K=%d outside 1..%d", K, kMaxK);
-    if (!pair_family(upd_dtype)) return fail(FA_EDTYPE, "fa_centered_clip_geometry: unsupported dtype %d", upd_dtype);
-    const CcGeom gm = cc_geom_dt(upd_dtype, K);
-    if (tile_elems) *tile_elems = gm.TE;
-    if (chain_terms) *chain_terms = kWmChain;
-    if (max_workgroups) *max_workgroups = gm.GRID;
-    if (flush_tiles) *flush_tiles = gm.FT;
-    return FA_OK;
+    return wm_geometry("fa_centered_clip_geometry", upd_dtype, K, K + 1, tile_elems, chain_terms, max_workgroups,
+                       flush_tiles);
 }
 
 int fa_tune(int knob, int value) {

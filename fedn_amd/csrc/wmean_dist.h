@@ -2,7 +2,9 @@
 // (fa_weighted_mean_sqdist, kernel k_wmean_dist): one smoothed Weiszfeld step of the geometric median.
 //
 // Included by fedagg.hip inside its anonymous namespace, after pair_dist.h (it uses that file's
-// conversions, 16-byte loads and fused multiply-add, fold_rules.h's element types and fedagg.hip's error plumbing).
+// conversions, 16-byte loads and fused multiply-add, fold_rules.h's element types, host_common.h's for_dtype and
+// fedagg.hip's error plumbing). Its host side — geometry, table builder, KP dispatch, the finishing launch and
+// the step entry points' argument checks — also serves cclip.h's kernel.
 // With C the compute type of the dtype family (f32 for f32 / f16 / bf16, f64 for f64 / i32 / i64) and
 // b_k = C(beta[k]):
 //     z[p] = O(((b_a C(u_a[p]) + b_b C(u_b[p])) + ...))   over the clients with b_k != 0, in index order,
@@ -46,10 +48,11 @@ struct WmGeom {
                  // partition must not depend on the device)
 };
 
-inline WmGeom wm_geom(int K, int csize, int waves) {
+// `cols`: columns of the tile, K (k_wmean_dist) or K + 1 (k_cclip_dist, cclip.h: the centre's)
+inline WmGeom wm_geom(int K, int csize, int waves, int cols) {
     WmGeom g;
     const int KP = wm_kp(K);
-    g.KS = K | 1;
+    g.KS = cols | 1;
     const int te = kWmTileBytes / (g.KS * csize);
     g.TE = (te < kWmTileMax ? te : kWmTileMax) / 8 * 8;
     const int sl = kBlock / (KP / wm_ck(KP));          // elements the lanes cover at a time
@@ -231,55 +234,98 @@ k_wmean_finish(double* __restrict__ dist, const double* __restrict__ work, const
     dist[k] = accumulate ? dist[k] + sum : sum;
 }
 
-// the geometry of (dtype, K); dtype is one of the six
-inline WmGeom wm_geom_dt(int dtype, int K) {
-    const int KP = wm_kp(K);
-    switch (dtype) {
-        case FA_F32: return wm_geom(K, 4, wm_waves<float>(KP));
-        case FA_F16: return wm_geom(K, 4, wm_waves<f16>(KP));
-        case FA_BF16: return wm_geom(K, 4, wm_waves<bf16>(KP));
-        case FA_F64: return wm_geom(K, 8, wm_waves<double>(KP));
-        case FA_I32: return wm_geom(K, 8, wm_waves<int32_t>(KP));
-        default: return wm_geom(K, 8, wm_waves<int64_t>(KP));
-    }
+// the geometry of (dtype, K) at `cols` tile columns; dtype is one of the six
+inline WmGeom wm_geom_dt(int dtype, int K, int cols) {
+    return for_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return wm_geom(K, (int)sizeof(typename WmTraits<T>::C), wm_waves<T>(wm_kp(K)), cols);
+    });
 }
 
 inline int64_t wm_workgroups(int64_t P, const WmGeom& gm) {
     return std::min<int64_t>((P + gm.TE - 1) / gm.TE, gm.GRID);
 }
 
-template <typename T, int KP>
-void launch_wmean_dist_kp(void* out, double* work, const WmTable<typename WmTraits<T>::C>& tab, int K, int kfirst,
-                          unsigned long long live, int64_t P, const WmGeom& gm, int nwg, bool vec, hipStream_t st) {
-    using O = typename WmTraits<T>::O;
-    hipLaunchKernelGGL((k_wmean_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st, static_cast<O*>(out), work,
-                       tab, K, kfirst, live, P, gm.TE, gm.KS, gm.FT, (int)vec);
+// The table of a launch from the update pointers and the coefficients already cast to C (bc[k] is C(beta[k])
+// held in a double: the cast back is exact). Returns vec (every update 16-byte aligned) and live: bit k for
+// every client with a nonzero coefficient — with skip_first, but for the first of them (k_wmean_dist starts its
+// sum with that client; k_cclip_dist starts with the centre).
+struct WmLive {
+    bool vec;
+    unsigned long long live;
+};
+
+template <typename C>
+WmLive wm_fill_table(WmTable<C>& tab, const void* const* ups, const double* bc, int K, bool skip_first) {
+    WmLive r{true, 0};
+    for (int k = 0; k < kMaxK; ++k) {
+        tab.ptr[k] = k < K ? ups[k] : nullptr;
+        tab.b[k] = k < K ? (C)bc[k] : C(0);
+        if (k >= K) continue;
+        r.vec = r.vec && aligned16(ups[k]);
+        if (bc[k] == 0.0) continue;
+        if (skip_first) skip_first = false;
+        else r.live |= 1ull << k;
+    }
+    return r;
+}
+
+// f(std::integral_constant<int, KP>) for the padded client count of K
+template <typename F>
+void wm_for_kp(int K, F&& f) {
+    switch (wm_kp(K)) {
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        case 16: f(std::integral_constant<int, 16>{}); break;
+        case 32: f(std::integral_constant<int, 32>{}); break;
+        default: f(std::integral_constant<int, 64>{}); break;
+    }
+}
+
+// the launch that follows either distance kernel: dist[k] from the nwg partials; `who` names the failed launch
+inline int wm_finish(double* dist, double* work, int K, int nwg, int accumulate, hipStream_t st, const char* who) {
+    hipLaunchKernelGGL(k_wmean_finish, dim3(1), dim3(kMaxK), 0, st, dist, work, K, nwg, accumulate);
+    return check_launch(who);
+}
+
+// The argument checks of the two step entry points, reported in `who`'s name: `ptrs` (every pointer the entry
+// point needs is there), K, P, the dtype family, the output dtype that goes with the updates' (`gives`: what the
+// updates do to it, for the message), and the K coefficients `coef` (called `cname`): each finite and >= 0, cast
+// to the compute type once into cc[k], where it must still be finite.
+inline int wm_check_step(const char* who, const char* cname, const char* gives, bool ptrs, int out_dtype, int upd_dtype,
+                         const double* coef, int K, int64_t P, double* cc) {
+    if (!ptrs) return fail(FA_EINVAL, "%s: null pointer argument", who);
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "%s: K=%d outside 1..%d", who, K, kMaxK);
+    if (P < 0) return fail(FA_EINVAL, "%s: negative size (P=%lld)", who, (long long)P);
+    const int fam = pair_family(upd_dtype);
+    if (!fam) return fail(FA_EDTYPE, "%s: unsupported dtype %d", who, upd_dtype);
+    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
+    if (out_dtype != want)
+        return fail(FA_EDTYPE, "%s: updates of dtype %d %s of dtype %d, not %d", who, upd_dtype, gives, want, out_dtype);
+    for (int k = 0; k < K; ++k) {
+        if (!(coef[k] >= 0.0) || std::isinf(coef[k]))
+            return fail(FA_EINVAL, "%s: %s[%d]=%g is negative or not finite", who, cname, k, coef[k]);
+        cc[k] = fam == 32 ? (double)(float)coef[k] : coef[k];
+        if (std::isinf(cc[k]))
+            return fail(FA_EINVAL, "%s: %s[%d]=%g is not finite in the compute type", who, cname, k, coef[k]);
+    }
+    return FA_OK;
 }
 
 template <typename T>
 int launch_wmean_dist(void* out, double* dist, const void* const* ups, const double* bc, int kfirst, int K, int64_t P,
                       int accumulate, double* work, hipStream_t st) {
     using C = typename WmTraits<T>::C;
+    using O = typename WmTraits<T>::O;
     WmTable<C> tab;
-    bool vec = true;
-    unsigned long long live = 0;
-    for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
-        tab.b[k] = k < K ? (C)bc[k] : C(0);            // (exact: bc[k] is C(beta[k]) held in a double)
-        if (k < K) vec = vec && aligned16(ups[k]);
-        if (k < K && k > kfirst && bc[k] != 0.0) live |= 1ull << k;
-    }
-    const WmGeom gm = wm_geom(K, (int)sizeof(C), wm_waves<T>(wm_kp(K)));
+    const WmLive tl = wm_fill_table(tab, ups, bc, K, true);
+    const WmGeom gm = wm_geom(K, (int)sizeof(C), wm_waves<T>(wm_kp(K)), K);
     const int nwg = (int)wm_workgroups(P, gm);
     g_kernel = "k_wmean_dist";
-    if (nwg > 0) {
-        switch (wm_kp(K)) {
-            case 8: launch_wmean_dist_kp<T, 8>(out, work, tab, K, kfirst, live, P, gm, nwg, vec, st); break;
-            case 16: launch_wmean_dist_kp<T, 16>(out, work, tab, K, kfirst, live, P, gm, nwg, vec, st); break;
-            case 32: launch_wmean_dist_kp<T, 32>(out, work, tab, K, kfirst, live, P, gm, nwg, vec, st); break;
-            default: launch_wmean_dist_kp<T, 64>(out, work, tab, K, kfirst, live, P, gm, nwg, vec, st); break;
-        }
-    }
-    hipLaunchKernelGGL(k_wmean_finish, dim3(1), dim3(kMaxK), 0, st, dist, work, K, nwg, accumulate);
-    return check_launch("fa_weighted_mean_sqdist: kernel launch");
+    if (nwg > 0)
+        wm_for_kp(K, [&](auto kp) {
+            constexpr int KP = decltype(kp)::value;
+            hipLaunchKernelGGL((k_wmean_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st,
+                               static_cast<O*>(out), work, tab, K, kfirst, tl.live, P, gm.TE, gm.KS, gm.FT, (int)tl.vec);
+        });
+    return wm_finish(dist, work, K, nwg, accumulate, st, "fa_weighted_mean_sqdist: kernel launch");
 }

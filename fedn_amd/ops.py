@@ -251,15 +251,20 @@ _SQDIST_F32 = (torch.float32, torch.float16, torch.bfloat16)
 _SQDIST_F64 = (torch.float64, torch.int32, torch.int64)
 
 
+def _geometry(entry, dtype, K):
+    """The four ints of the probe library's geometry query ``entry`` for K updates of ``dtype``."""
+    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _abi.check(getattr(_abi.load_probe(), entry)(fa_dtype(dtype), int(K), ctypes.byref(te), ctypes.byref(r),
+                                                 ctypes.byref(wg), ctypes.byref(ft)))
+    return te.value, r.value, wg.value, ft.value
+
+
 def sqdist_geometry(dtype, K):
     """``(TE, R, max workgroups, tiles per flush)`` of ``fa_pairwise_sqdist`` for K updates of ``dtype``:
     the elements a workgroup stages at a time, the longest chain summed in the compute type, the largest
     grid, and the tiles a workgroup walks before it flushes its chains to f64. A measurement entry point
     (libfedagg_probe.so, the same source as the product library): tools and tests place sizes with it."""
-    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _abi.check(_abi.load_probe().fa_pairwise_sqdist_geometry(fa_dtype(dtype), int(K), ctypes.byref(te),
-                                                             ctypes.byref(r), ctypes.byref(wg), ctypes.byref(ft)))
-    return te.value, r.value, wg.value, ft.value
+    return _geometry("fa_pairwise_sqdist_geometry", dtype, K)
 
 
 def sqdist_rtol(dtype, P):
@@ -275,6 +280,63 @@ def sqdist_rtol(dtype, P):
     raise TypeError(f"pairwise_sqdist: dtype {dt} is not supported")
 
 
+def _distance_updates(name, updates):
+    """The checks the three distance ops make of their updates, in ``name``'s words: 1..64 flat
+    contiguous tensors of one supported dtype, one length and one device. Returns ``(K, P, dev, upd_dt)``."""
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"{name} takes 1..{MAX_ORDER_K} updates, got {K}")
+    if not isinstance(updates[0], torch.Tensor):
+        raise TypeError("updates[0] must be a torch.Tensor")
+    P = updates[0].numel()
+    dev = updates[0].device
+    upd_dt = updates[0].dtype
+    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
+        raise TypeError(f"{name}: dtype {upd_dt} is not supported")
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError(f"all updates in one {name} call must share a dtype")
+    return K, P, dev, upd_dt
+
+
+def _check_point(name, arg, t, P, dev, upd_dt):
+    """``t`` (argument ``arg``) holds a point of the updates' space: P elements of their output dtype."""
+    _check_dev(arg, t, P, dev)
+    if t.dtype != order_mean_dtype(upd_dt):
+        raise TypeError(f"{name}: {arg} must be {order_mean_dtype(upd_dt)} for {upd_dt} updates, got {t.dtype}")
+
+
+def _check_outputs(name, dev, accumulate, arg, what, sums, n, out=None, P=0, upd_dt=None):
+    """The output checks of a distance op: ``out`` where given is a point (:func:`_check_point`); the
+    sums ``sums`` (argument ``arg``, "the ``what``" in words) are n float64 values, or None — then there is
+    nothing to ``accumulate`` into."""
+    if out is not None:
+        _check_point(name, "out", out, P, dev, upd_dt)
+    if sums is None:
+        if accumulate:
+            raise ValueError(f"{name}: accumulate needs the {what} to add to ({arg})")
+    else:
+        _check_dev(arg, sums, n, dev)
+        if sums.dtype != torch.float64:
+            raise TypeError(f"{name}: {arg} must be float64, got {sums.dtype}")
+
+
+def _stream_alloc(dev, stream, nwork, sums, shape, out=None, fresh_out=None):
+    """The launching stream ``s`` and, allocated under it (scratch and fresh outputs belong to the stream
+    that launches: DESIGN.md §3.7): ``out`` where None and wanted (``fresh_out``: its ``(P, dtype)``),
+    the float64 ``sums`` of ``shape`` where None, and ``nwork`` doubles of scratch. Returns
+    ``(s, out, sums, work)``; called on ``dev``."""
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        if out is None and fresh_out is not None:
+            out = torch.empty(fresh_out[0], dtype=fresh_out[1], device=dev)
+        if sums is None:
+            sums = torch.empty(shape, dtype=torch.float64, device=dev)
+        work = torch.empty(max(1, int(nwork)), dtype=torch.float64, device=dev)
+    return s, out, sums, work
+
+
 def pairwise_sqdist(updates, out=None, accumulate=False, stream=None):
     """Squared Euclidean distances between K updates on device (``fa_pairwise_sqdist``): a K x K
     float64 device tensor, exactly symmetric with a zero diagonal, every entry within
@@ -286,33 +348,10 @@ def pairwise_sqdist(updates, out=None, accumulate=False, stream=None):
     accumulate  add this call's distances to ``out`` instead of writing it (dtype groups, slices)
     """
     lib = _abi.load()
-    K = len(updates)
-    if not 1 <= K <= MAX_ORDER_K:
-        raise ValueError(f"pairwise_sqdist takes 1..{MAX_ORDER_K} updates, got {K}")
-    if not isinstance(updates[0], torch.Tensor):
-        raise TypeError("updates[0] must be a torch.Tensor")
-    P = updates[0].numel()
-    dev = updates[0].device
-    upd_dt = updates[0].dtype
-    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
-        raise TypeError(f"pairwise_sqdist: dtype {upd_dt} is not supported")
-    for i, u in enumerate(updates):
-        _check_dev(f"updates[{i}]", u, P, dev)
-        if u.dtype != upd_dt:
-            raise TypeError("all updates in one pairwise_sqdist call must share a dtype")
-    if out is None:
-        if accumulate:
-            raise ValueError("pairwise_sqdist: accumulate needs the matrix to add to (out)")
-    else:
-        _check_dev("out", out, K * K, dev)
-        if out.dtype != torch.float64:
-            raise TypeError(f"pairwise_sqdist: out must be float64, got {out.dtype}")
+    K, P, dev, upd_dt = _distance_updates("pairwise_sqdist", updates)
+    _check_outputs("pairwise_sqdist", dev, accumulate, "out", "matrix", out, K * K)
     with _on(dev):
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        with torch.cuda.stream(s):               # scratch (and a fresh D) belong to the launching stream
-            if out is None:
-                out = torch.empty((K, K), dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, int(lib.fa_pairwise_sqdist_work(K, P))), dtype=torch.float64, device=dev)
+        s, _, out, work = _stream_alloc(dev, stream, lib.fa_pairwise_sqdist_work(K, P), out, (K, K))
         rc = lib.fa_pairwise_sqdist(out.data_ptr(), _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt),
                                     K, P, int(bool(accumulate)), work.data_ptr(), ctypes_stream(s))
     _abi.check(rc)
@@ -325,10 +364,7 @@ def wmean_geometry(dtype, K):
     compute type (at most R of :func:`sqdist_rtol`), the largest grid, and the tiles a workgroup walks
     between two flushes of its chains to f64. A measurement entry point (libfedagg_probe.so) like
     :func:`sqdist_geometry`."""
-    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _abi.check(_abi.load_probe().fa_wmean_sqdist_geometry(fa_dtype(dtype), int(K), ctypes.byref(te), ctypes.byref(r),
-                                                          ctypes.byref(wg), ctypes.byref(ft)))
-    return te.value, r.value, wg.value, ft.value
+    return _geometry("fa_wmean_sqdist_geometry", dtype, K)
 
 
 def weighted_mean_sqdist(updates, beta, out=None, dist=None, accumulate=False, store=True, stream=None):
@@ -348,43 +384,15 @@ def weighted_mean_sqdist(updates, beta, out=None, dist=None, accumulate=False, s
     store       False: z is formed for the distances but not stored (``out`` is left alone; None is returned)
     """
     lib = _abi.load()
-    K = len(updates)
-    if not 1 <= K <= MAX_ORDER_K:
-        raise ValueError(f"weighted_mean_sqdist takes 1..{MAX_ORDER_K} updates, got {K}")
-    if not isinstance(updates[0], torch.Tensor):
-        raise TypeError("updates[0] must be a torch.Tensor")
-    P = updates[0].numel()
-    dev = updates[0].device
-    upd_dt = updates[0].dtype
-    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
-        raise TypeError(f"weighted_mean_sqdist: dtype {upd_dt} is not supported")
+    K, P, dev, upd_dt = _distance_updates("weighted_mean_sqdist", updates)
     out_dt = order_mean_dtype(upd_dt)
-    for i, u in enumerate(updates):
-        _check_dev(f"updates[{i}]", u, P, dev)
-        if u.dtype != upd_dt:
-            raise TypeError("all updates in one weighted_mean_sqdist call must share a dtype")
     beta = [float(b) for b in beta]
     if len(beta) != K:
         raise ValueError(f"weighted_mean_sqdist: {len(beta)} weights for {K} updates")
-    if out is not None:
-        _check_dev("out", out, P, dev)
-        if out.dtype != out_dt:
-            raise TypeError(f"weighted_mean_sqdist: out must be {out_dt} for {upd_dt} updates, got {out.dtype}")
-    if dist is None:
-        if accumulate:
-            raise ValueError("weighted_mean_sqdist: accumulate needs the distances to add to (dist)")
-    else:
-        _check_dev("dist", dist, K, dev)
-        if dist.dtype != torch.float64:
-            raise TypeError(f"weighted_mean_sqdist: dist must be float64, got {dist.dtype}")
+    _check_outputs("weighted_mean_sqdist", dev, accumulate, "dist", "distances", dist, K, out, P, upd_dt)
     with _on(dev):
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        with torch.cuda.stream(s):               # scratch and fresh outputs belong to the launching stream
-            if out is None and store:
-                out = torch.empty(P, dtype=out_dt, device=dev)
-            if dist is None:
-                dist = torch.empty(K, dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, int(lib.fa_wmean_sqdist_work(K, P))), dtype=torch.float64, device=dev)
+        s, out, dist, work = _stream_alloc(dev, stream, lib.fa_wmean_sqdist_work(K, P), dist, K, out,
+                                           (P, out_dt) if store else None)
         rc = lib.fa_weighted_mean_sqdist(out.data_ptr() if store else None, fa_dtype(out_dt), dist.data_ptr(),
                                          _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt),
                                          _abi.double_array(beta), K, P, int(bool(accumulate)), work.data_ptr(),
@@ -397,10 +405,7 @@ def cclip_geometry(dtype, K):
     """``(TE, chain, max workgroups, tiles per flush)`` of ``fa_centered_clip_step`` for K updates of
     ``dtype``, as :func:`wmean_geometry` (its tile holds one more column, the centre's). A measurement
     entry point (libfedagg_probe.so)."""
-    te, r, wg, ft = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
-    _abi.check(_abi.load_probe().fa_centered_clip_geometry(fa_dtype(dtype), int(K), ctypes.byref(te), ctypes.byref(r),
-                                                           ctypes.byref(wg), ctypes.byref(ft)))
-    return te.value, r.value, wg.value, ft.value
+    return _geometry("fa_centered_clip_geometry", dtype, K)
 
 
 def centered_clip_step(updates, center, coef, out=None, dist=None, accumulate=False, store=True, stream=None):
@@ -422,46 +427,16 @@ def centered_clip_step(updates, center, coef, out=None, dist=None, accumulate=Fa
     store       False: v' is formed for the distances but not stored (``out`` is left alone; None is returned)
     """
     lib = _abi.load()
-    K = len(updates)
-    if not 1 <= K <= MAX_ORDER_K:
-        raise ValueError(f"centered_clip_step takes 1..{MAX_ORDER_K} updates, got {K}")
-    if not isinstance(updates[0], torch.Tensor):
-        raise TypeError("updates[0] must be a torch.Tensor")
-    P = updates[0].numel()
-    dev = updates[0].device
-    upd_dt = updates[0].dtype
-    if upd_dt not in _SQDIST_F32 and upd_dt not in _SQDIST_F64:
-        raise TypeError(f"centered_clip_step: dtype {upd_dt} is not supported")
+    K, P, dev, upd_dt = _distance_updates("centered_clip_step", updates)
     out_dt = order_mean_dtype(upd_dt)
-    for i, u in enumerate(updates):
-        _check_dev(f"updates[{i}]", u, P, dev)
-        if u.dtype != upd_dt:
-            raise TypeError("all updates in one centered_clip_step call must share a dtype")
-    _check_dev("center", center, P, dev)
-    if center.dtype != out_dt:
-        raise TypeError(f"centered_clip_step: center must be {out_dt} for {upd_dt} updates, got {center.dtype}")
+    _check_point("centered_clip_step", "center", center, P, dev, upd_dt)
     coef = [float(c) for c in coef]
     if len(coef) != K:
         raise ValueError(f"centered_clip_step: {len(coef)} coefficients for {K} updates")
-    if out is not None:
-        _check_dev("out", out, P, dev)
-        if out.dtype != out_dt:
-            raise TypeError(f"centered_clip_step: out must be {out_dt} for {upd_dt} updates, got {out.dtype}")
-    if dist is None:
-        if accumulate:
-            raise ValueError("centered_clip_step: accumulate needs the distances to add to (dist)")
-    else:
-        _check_dev("dist", dist, K, dev)
-        if dist.dtype != torch.float64:
-            raise TypeError(f"centered_clip_step: dist must be float64, got {dist.dtype}")
+    _check_outputs("centered_clip_step", dev, accumulate, "dist", "distances", dist, K, out, P, upd_dt)
     with _on(dev):
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        with torch.cuda.stream(s):               # scratch and fresh outputs belong to the launching stream
-            if out is None and store:
-                out = torch.empty(P, dtype=out_dt, device=dev)
-            if dist is None:
-                dist = torch.empty(K, dtype=torch.float64, device=dev)
-            work = torch.empty(max(1, int(lib.fa_centered_clip_work(K, P))), dtype=torch.float64, device=dev)
+        s, out, dist, work = _stream_alloc(dev, stream, lib.fa_centered_clip_work(K, P), dist, K, out,
+                                           (P, out_dt) if store else None)
         # (an empty tensor has no address and the library refuses a null centre: at P = 0 nothing reads it)
         cptr = center.data_ptr() if P else work.data_ptr()
         rc = lib.fa_centered_clip_step((out.data_ptr() or None) if store else None, cptr, fa_dtype(out_dt),

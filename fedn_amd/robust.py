@@ -43,6 +43,7 @@ stream waits for an update's ``ready`` event before the launch that reads it; th
 for the launch that last read a ring buffer before it refills it; everything the launches read is
 held until the result is on the host.
 """
+import math
 import time
 
 import numpy as np
@@ -67,14 +68,12 @@ class UnsupportedRound(TypeError):
 def trim_count(trim_fraction, K):
     """Values dropped at EACH end of K sorted values: ``floor(trim_fraction * K)``, never more than
     ``(K - 1) // 2`` (at least one value is kept whatever the product's rounding does)."""
-    import math
     return max(0, min(math.floor(trim_fraction * K), (K - 1) // 2))
 
 
 def krum_f(byzantine_fraction, K):
     """Byzantine clients Krum assumes among K: ``floor(byzantine_fraction * K)``, never more than the
     paper's condition ``2f + 2 < K`` allows (``(K - 3) // 2``); 0 below K = 3."""
-    import math
     if K < 3:
         return 0
     return max(0, min(math.floor(byzantine_fraction * K), (K - 3) // 2))
@@ -235,31 +234,59 @@ class RobustPipeline:
         return arrays
 
     # ---- reduction -------------------------------------------------------------------
-    def result(self, trim):
-        """The round's model as host arrays in the layout's shapes (dtypes: ``ops.order_mean_dtype``):
-        per element the mean of the sorted values ``s[trim] .. s[K - trim - 1]``."""
+    def _clients(self):
+        """K, the round's size, within what one launch's table holds: every rule's first check, ahead of
+        those of its own arguments."""
         K = len(self.updates)
         if not 1 <= K <= ops.MAX_ORDER_K:
             raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
-        if trim < 0 or 2 * trim >= K:
-            raise ValueError(f"trim={trim} leaves nothing of {K} updates")
+        return K
+
+    def _round(self, body, center=None):
+        """The frame of every rule, around its arithmetic ``body``: on the round's device and compute
+        stream, wait for every staged update's ``ready`` event, run ``body()`` — it returns the result's
+        dtype groups as pinned host tensors, their copies still in flight — synchronise the compute stream
+        (timed as D2H) and unpack the groups into host arrays of the layout's shapes.
+
+        ``center`` (centred clipping: the global model's dtype groups as pinned host tensors) is uploaded
+        ahead of the waits, allocated on the compute stream that writes and reads it, handed to
+        ``body(cen)`` as device tensors by dtype group and copied back into its host tensors ahead of the
+        closing synchronise: those are then the result.
+
+        When anything inside fails, what was enqueued drains before the caller may free anything it reads."""
         out = [None] * len(self.layout.shapes)
         try:
             with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
+                if center is not None:
+                    cen = {}
+                    for dt, host in center.items():
+                        cen[dt] = torch.empty(host.numel(), dtype=host.dtype, device=self.device)
+                        cen[dt].copy_(host, non_blocking=True)
                 for u in self.updates:
                     if isinstance(u, StagedModel):
                         self.compute.wait_event(u.ready)
-                hosts = {dt: self._reduce_group(dt, trim) for dt in self.layout.groups}
+                hosts = body() if center is None else body(cen)
                 tic = time.perf_counter()
+                if center is not None:
+                    hosts = center
+                    for dt, host in center.items():
+                        host.copy_(cen[dt], non_blocking=True)
                 self.compute.synchronize()
                 self.time_d2h += time.perf_counter() - tic
         except BaseException:
-            # a failed launch: what was enqueued drains before the caller may free anything it reads
             torch.cuda.synchronize(self.device)
             raise
         for dt in self.layout.groups:
             self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
         return out
+
+    def result(self, trim):
+        """The round's model as host arrays in the layout's shapes (dtypes: ``ops.order_mean_dtype``):
+        per element the mean of the sorted values ``s[trim] .. s[K - trim - 1]``."""
+        K = self._clients()
+        if trim < 0 or 2 * trim >= K:
+            raise ValueError(f"trim={trim} leaves nothing of {K} updates")
+        return self._round(lambda: {dt: self._reduce_group(dt, trim) for dt in self.layout.groups})
 
     def select_mean(self, f, m):
         """Krum (``m = 1``) / Multi-Krum (``m = K - f``): the unweighted mean of the ``m`` updates that
@@ -273,43 +300,51 @@ class RobustPipeline:
         (``A(y) / 1``, the converting copy, for Krum's single one). A selected update that sits on the
         host is therefore uploaded a second time, slice by slice: HBM stays bounded by the budget plus
         the ring. Raises ``ValueError`` when fewer than ``m`` clients have a finite score."""
-        K = len(self.updates)
-        if not 1 <= K <= ops.MAX_ORDER_K:
-            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        K = self._clients()
         if not (0 <= f < K and 1 <= m <= K):
             raise ValueError(f"f={f}, m={m} of {K} updates")
-        out = [None] * len(self.layout.shapes)
-        try:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                for u in self.updates:
-                    if isinstance(u, StagedModel):
-                        self.compute.wait_event(u.ready)
-                Dh = self._distance_matrix(K)
-                self.scores = krum_scores(Dh, f)
-                self.selected = krum_select(Dh, f, m)
-                hosts = {dt: self._reduce_group(dt, 0, self.selected) for dt in self.layout.groups}
-                tic = time.perf_counter()
-                self.compute.synchronize()
-                self.time_d2h += time.perf_counter() - tic
-        except BaseException:
-            torch.cuda.synchronize(self.device)
-            raise
-        for dt in self.layout.groups:
-            self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
-        return out
 
-    def _distance_matrix(self, K):
-        """The K x K matrix of squared distances between the held updates, on the host: one pass over
-        the dtype groups, summed into one matrix on the device. Called on the compute stream with the
-        staged updates' ``ready`` events already waited for."""
-        D = torch.zeros((K, K), dtype=torch.float64, device=self.device)
+        def body():
+            Dh = self._distance_matrix(K)
+            self.scores = krum_scores(Dh, f)
+            self.selected = krum_select(Dh, f, m)
+            return {dt: self._reduce_group(dt, 0, self.selected) for dt in self.layout.groups}
+
+        return self._round(body)
+
+    def _distance_pass(self, shape, group, coef=None):
+        """One pass over the dtype groups that sums squared distances into a zeroed float64 device tensor
+        of ``shape``, and that tensor on the host. ``group(dt)`` gives ``(step, after)`` of a dtype group:
+        ``step(b, lo, hi, views, stride, acc, accumulate)`` launches one slice's op on the accumulator —
+        written by the pass's first launch, added to by the rest — and ``after`` is :meth:`_walk_group`'s.
+        With ``coef``, ``(coef, sums)`` is appended to ``trace``. Called inside :meth:`_round`: on the
+        compute stream, the staged updates' ``ready`` events already waited for."""
+        acc = torch.zeros(shape, dtype=torch.float64, device=self.device)
         written = False
         for dt in self.layout.groups:
-            written = self._distance_group(dt, D, written)
+            step, after = group(dt)
+            if self.layout.group_elems[dt] == 0:     # only empty tensors: no launch
+                continue
+
+            def launch(b, lo, hi, views, stride):
+                nonlocal written
+                step(b, lo, hi, views, stride, acc, written)
+                written = True
+
+            self._walk_group(dt, None, launch, after)
         tic = time.perf_counter()
-        Dh = D.cpu().numpy()                         # (synchronises the compute stream)
+        sums = acc.cpu().numpy()                     # (synchronises the compute stream)
         self.time_d2h += time.perf_counter() - tic
-        return Dh
+        if coef is not None:
+            self.trace.append((coef, sums))
+        return sums
+
+    def _distance_matrix(self, K):
+        """The K x K matrix of squared distances between the held updates, on the host."""
+        def step(b, lo, hi, views, stride, D, accumulate):
+            ops.pairwise_sqdist(views, out=D, accumulate=accumulate, stream=self.compute)
+
+        return self._distance_pass((K, K), lambda dt: (step, None))
 
     def geometric_median(self, iterations, nu):
         """The smoothed geometric median of the held updates (RFA: Pillutla, Kakade and Harchaoui) by
@@ -331,51 +366,39 @@ class RobustPipeline:
 
         Kept on the pipeline: ``weights`` (the last pass's beta), ``distances`` (sqrt of the last pass's
         d), ``excluded`` (FIFO indices) and ``trace`` (one ``(beta, d)`` pair per pass, float64)."""
-        K = len(self.updates)
-        if not 1 <= K <= ops.MAX_ORDER_K:
-            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        K = self._clients()
         if iterations < 0 or not (nu > 0 and np.isfinite(nu)):
             raise ValueError(f"iterations={iterations}, nu={nu}")
         T = 0 if K == 1 else int(iterations)
         self.weights, self.distances, self.excluded, self.trace = None, None, [], []
-        out = [None] * len(self.layout.shapes)
-        try:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                for u in self.updates:
-                    if isinstance(u, StagedModel):
-                        self.compute.wait_event(u.ready)
-                beta = np.full(K, 1.0 / K, dtype=np.float64)
+
+        def body():
+            beta = np.full(K, 1.0 / K, dtype=np.float64)
+            d, hosts = self._weiszfeld_pass(beta, T == 0)
+            if not np.isfinite(d).all():
+                Dh = self._distance_matrix(K)
+                off = ~np.eye(K, dtype=bool)
+                bad = [k for k in range(K) if K > 1 and not np.isfinite(Dh[k][off[k]]).any()]
+                if not bad or len(bad) == K:
+                    raise ValueError(f"non-finite distances to the mean ({d}) and {len(bad)} of {K} clients "
+                                     "are non-finite against every other: nothing to exclude")
+                self.trace = []
+                self.excluded = bad
+                beta = np.full(K, 1.0 / (K - len(bad)), dtype=np.float64)
+                beta[bad] = 0.0
                 d, hosts = self._weiszfeld_pass(beta, T == 0)
-                if not np.isfinite(d).all():
-                    Dh = self._distance_matrix(K)
-                    off = ~np.eye(K, dtype=bool)
-                    bad = [k for k in range(K) if K > 1 and not np.isfinite(Dh[k][off[k]]).any()]
-                    if not bad or len(bad) == K:
-                        raise ValueError(f"non-finite distances to the mean ({d}) and {len(bad)} of {K} clients "
-                                         "are non-finite against every other: nothing to exclude")
-                    self.trace = []
-                    self.excluded = bad
-                    beta = np.full(K, 1.0 / (K - len(bad)), dtype=np.float64)
-                    beta[bad] = 0.0
-                    d, hosts = self._weiszfeld_pass(beta, T == 0)
-                    good = np.ones(K, dtype=bool)
-                    good[bad] = False
-                    if not np.isfinite(d[good]).all():
-                        raise ValueError(f"non-finite distances remain after excluding clients {bad}: {d}")
-                for t in range(1, T + 1):
-                    beta = weiszfeld_weights(d, nu)
-                    d, hosts = self._weiszfeld_pass(beta, t == T)
-                tic = time.perf_counter()
-                self.compute.synchronize()
-                self.time_d2h += time.perf_counter() - tic
-        except BaseException:
-            torch.cuda.synchronize(self.device)
-            raise
-        self.weights = beta
+                good = np.ones(K, dtype=bool)
+                good[bad] = False
+                if not np.isfinite(d[good]).all():
+                    raise ValueError(f"non-finite distances remain after excluding clients {bad}: {d}")
+            for t in range(1, T + 1):
+                d, hosts = self._weiszfeld_pass(weiszfeld_weights(d, nu), t == T)
+            return hosts
+
+        out = self._round(body)
+        self.weights, d = self.trace[-1]             # the last pass's (beta, d)
         with np.errstate(invalid="ignore"):
             self.distances = np.sqrt(d)
-        for dt in self.layout.groups:
-            self.layout.unpack_group(hosts[dt].numpy(), dt, out, copy=False)
         return out
 
     def _weiszfeld_pass(self, beta, store):
@@ -383,38 +406,28 @@ class RobustPipeline:
         squared distances to the weighted mean as a float64 host array, and (``store``) the mean's
         groups as pinned host tensors, valid once the compute stream is synchronised. Appends
         ``(beta, d)`` to ``trace``."""
-        K = len(self.updates)
         beta = np.array(beta, dtype=np.float64)
-        dist = torch.zeros(K, dtype=torch.float64, device=self.device)
-        state = [False]                              # dist is written by the pass's first launch, added to after
         hosts = {}
-        for dt in self.layout.groups:
-            n = self.layout.group_elems[dt]
-            odt = self._out_dt[dt]
-            host = hosts[dt] = torch.empty(n, dtype=odt, pin_memory=True) if store else None
-            if n == 0:
-                continue
-            outs = {}
 
-            def launch(b, lo, hi, views, step, odt=odt, outs=outs):
+        def group(dt):
+            odt, outs = self._out_dt[dt], {}
+            host = hosts[dt] = torch.empty(self.layout.group_elems[dt], dtype=odt, pin_memory=True) if store else None
+
+            def step(b, lo, hi, views, stride, dist, accumulate):
                 z = None
                 if store:
                     if b not in outs:
-                        outs[b] = torch.empty(step, dtype=odt, device=self.device)
+                        outs[b] = torch.empty(stride, dtype=odt, device=self.device)
                     z = outs[b][:hi - lo]
-                ops.weighted_mean_sqdist(views, beta, out=z, dist=dist, accumulate=state[0], store=store,
+                ops.weighted_mean_sqdist(views, beta, out=z, dist=dist, accumulate=accumulate, store=store,
                                          stream=self.compute)
-                state[0] = True
 
-            def after(b, lo, hi, host=host, outs=outs):
+            def after(b, lo, hi):
                 host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
 
-            self._walk_group(dt, None, launch, after if store else None)
-        tic = time.perf_counter()
-        d = dist.cpu().numpy()                       # (synchronises the compute stream)
-        self.time_d2h += time.perf_counter() - tic
-        self.trace.append((beta, d))
-        return d, hosts
+            return step, after if store else None
+
+        return self._distance_pass(len(self.updates), group, beta), hosts
 
     def centered_clip(self, center_arrays, iterations, tau):
         """Centred clipping of the held updates around the previous global model ``center_arrays``
@@ -438,48 +451,27 @@ class RobustPipeline:
 
         Kept on the pipeline: ``coefficients`` (the last pass's), ``distances`` (sqrt of the last pass's
         d), ``excluded`` (FIFO indices) and ``trace`` (one ``(coef, d)`` pair per pass, float64)."""
-        K = len(self.updates)
-        if not 1 <= K <= ops.MAX_ORDER_K:
-            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        K = self._clients()
         if iterations < 0 or not (tau > 0 and np.isfinite(tau)):
             raise ValueError(f"iterations={iterations}, tau={tau}")
         L = int(iterations)
         self.coefficients, self.distances, self.excluded, self.trace = None, None, [], []
-        packed = self._pack_center(center_arrays)
-        out = [None] * len(self.layout.shapes)
-        try:
-            with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
-                cen = {}
-                for dt, host in packed.items():      # allocated on the stream that writes and reads it
-                    cen[dt] = torch.empty(host.numel(), dtype=host.dtype, device=self.device)
-                    cen[dt].copy_(host, non_blocking=True)
-                for u in self.updates:
-                    if isinstance(u, StagedModel):
-                        self.compute.wait_event(u.ready)
-                coef = np.zeros(K, dtype=np.float64)
-                d = self._clip_pass(coef, cen, False)
-                good = np.isfinite(d)
-                self.excluded = [k for k in range(K) if not good[k]]
-                if not good.any():
-                    raise ValueError(f"no client has a finite distance to the global model: {d}")
-                for _ in range(L):
-                    coef = clip_coefficients(d, tau)
-                    d = self._clip_pass(coef, cen, True)
-                    if not np.isfinite(d[good]).all():
-                        raise ValueError(f"a distance turned non-finite after a clipping step: {d}")
-                tic = time.perf_counter()
-                for dt, host in packed.items():
-                    host.copy_(cen[dt], non_blocking=True)
-                self.compute.synchronize()
-                self.time_d2h += time.perf_counter() - tic
-        except BaseException:
-            torch.cuda.synchronize(self.device)
-            raise
-        self.coefficients = coef
+
+        def body(cen):
+            d = self._clip_pass(np.zeros(K, dtype=np.float64), cen, False)
+            good = np.isfinite(d)
+            self.excluded = [k for k in range(K) if not good[k]]
+            if not good.any():
+                raise ValueError(f"no client has a finite distance to the global model: {d}")
+            for _ in range(L):
+                d = self._clip_pass(clip_coefficients(d, tau), cen, True)
+                if not np.isfinite(d[good]).all():
+                    raise ValueError(f"a distance turned non-finite after a clipping step: {d}")
+
+        out = self._round(body, self._pack_center(center_arrays))
+        self.coefficients, d = self.trace[-1]        # the last pass's (coef, d)
         with np.errstate(invalid="ignore"):
             self.distances = np.sqrt(d)
-        for dt in self.layout.groups:
-            self.layout.unpack_group(packed[dt].numpy(), dt, out, copy=False)
         return out
 
     def _pack_center(self, center_arrays):
@@ -509,27 +501,17 @@ class RobustPipeline:
         """One fused pass over every dtype group with the coefficients ``coef``: the K squared distances to
         the new point as a float64 host array; with ``store`` the centre ``cen`` (device tensors by dtype
         group) is moved in place. Appends ``(coef, d)`` to ``trace``."""
-        K = len(self.updates)
         coef = np.array(coef, dtype=np.float64)
-        dist = torch.zeros(K, dtype=torch.float64, device=self.device)
-        state = [False]                              # dist is written by the pass's first launch, added to after
-        for dt in self.layout.groups:
-            if self.layout.group_elems[dt] == 0:
-                continue
-            c = cen[dt]
 
-            def launch(b, lo, hi, views, step, c=c):
-                v = c[lo:hi]
-                ops.centered_clip_step(views, v, coef, out=v if store else None, dist=dist, accumulate=state[0],
+        def group(dt):
+            def step(b, lo, hi, views, stride, dist, accumulate):
+                v = cen[dt][lo:hi]
+                ops.centered_clip_step(views, v, coef, out=v if store else None, dist=dist, accumulate=accumulate,
                                        store=store, stream=self.compute)
-                state[0] = True
 
-            self._walk_group(dt, None, launch, None)
-        tic = time.perf_counter()
-        d = dist.cpu().numpy()                       # (synchronises the compute stream)
-        self.time_d2h += time.perf_counter() - tic
-        self.trace.append((coef, d))
-        return d
+            return step, None
+
+        return self._distance_pass(len(self.updates), group, coef)
 
     def _host_flat(self, arrays, dt):
         """(flat array, element offset in the group) of the non-empty members of group ``dt``."""
@@ -558,20 +540,6 @@ class RobustPipeline:
 
         self._walk_group(dt, subset, launch, after)
         return host
-
-    def _distance_group(self, dt, D, written):
-        """Add group ``dt``'s squared distances to ``D`` (written, not added to, by the first launch of
-        the round); returns whether ``D`` has been written."""
-        if self.layout.group_elems[dt] == 0:
-            return written
-        state = [written]
-
-        def launch(b, lo, hi, views, step):
-            ops.pairwise_sqdist(views, out=D, accumulate=state[0], stream=self.compute)
-            state[0] = True
-
-        self._walk_group(dt, None, launch, None)
-        return state[0]
 
     def _walk_group(self, dt, subset, launch, after):
         """Run ``launch(b, lo, hi, views, step)`` over group ``dt`` of the updates at ``subset`` (all when
