@@ -128,6 +128,10 @@ EXPORTS = {
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_double),   # updates, upd_dtype, coef
         ctypes.c_int, ctypes.c_int64, ctypes.c_int,                        # K, P, accumulate
         ctypes.c_void_p, ctypes.c_void_p]),                                # work, stream
+    "fa_median_window_mean": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
+        ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # K, keep, P, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -151,7 +155,7 @@ PROBE_EXPORTS = {
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

@@ -54,7 +54,8 @@ class Aggregator(AggregatorBase):
 
     default_parameters = DEFAULT_PARAMETERS
     parameter_schema = PARAMETER_SCHEMA
-    fraction_parameter = "trim_fraction"      # the one parameter, a float in [0, 0.5) (subclasses rename it)
+    fraction_parameter = "trim_fraction"      # the one parameter, a float in [0, fraction_bound) (subclasses rename it)
+    fraction_bound = 0.5                      # ... and its exclusive upper bound (bulyan.py lowers it)
 
     def __init__(self, update_handler, device=None, hbm_budget=None):
         super().__init__(update_handler)
@@ -96,8 +97,8 @@ class Aggregator(AggregatorBase):
             parameters = {}
         merged = {**self.default_parameters, **parameters}
         f = merged.get(self.fraction_parameter)
-        if f is not None and not 0.0 <= f < 0.5:       # (a NaN fails both comparisons)
-            raise InvalidParameterError(f"Parameter {self.fraction_parameter} must lie in [0, 0.5), got {f}")
+        if f is not None and not 0.0 <= f < self.fraction_bound:       # (a NaN fails both comparisons)
+            raise InvalidParameterError(f"Parameter {self.fraction_parameter} must lie in [0, {self.fraction_bound}), got {f}")
         return merged
 
     def _drain(self):

@@ -88,6 +88,7 @@ size_t dt_size(int dt) {
 #include "fedavg_launch.h"    // store window, parked grid, geometry by size, launch_fedavg
 #include "fedopt_launch.h"    // store window, launch_fedopt
 #include "order_mean.h"       // coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
+#include "median_window.h"    // mean of the values closest to the median, Bulyan (k_median_window, fa_median_window_mean)
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
 #include "cclip.h"            // one centred-clipping step and the K squared distances to it (k_cclip_dist, fa_centered_clip_step)
@@ -707,6 +708,27 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
     if (P == 0) return FA_OK;
     if (const int rc = check_updates("fa_trimmed_mean", updates, K)) return rc;
     return for_dtype(upd_dtype, [&](auto t) { return launch_order_mean<decltype(t)>(out, updates, K, trim, P, st); });
+}
+
+
+int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int keep,
+                          int64_t P, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!out || !updates) return fail(FA_EINVAL, "fa_median_window_mean: null pointer argument");
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_median_window_mean: K=%d outside 1..%d", K, kMaxK);
+    if (keep < 1 || keep > K) return fail(FA_EINVAL, "fa_median_window_mean: keep=%d outside 1..K=%d", keep, K);
+    if (P < 0) return fail(FA_EINVAL, "fa_median_window_mean: negative size (P=%lld)", (long long)P);
+    const bool pair = (upd_dtype == FA_F32 && out_dtype == FA_F32) || (upd_dtype == FA_F64 && out_dtype == FA_F64) ||
+                      (upd_dtype == FA_F16 && out_dtype == FA_F16) || (upd_dtype == FA_BF16 && out_dtype == FA_F32) ||
+                      ((upd_dtype == FA_I32 || upd_dtype == FA_I64) && out_dtype == FA_F64);
+    if (!pair)
+        return fail(FA_EDTYPE, "fa_median_window_mean: unsupported dtype pair (update %d, output %d)", upd_dtype,
+                    out_dtype);
+    if (P == 0) return FA_OK;
+    if (const int rc = check_updates("fa_median_window_mean", updates, K)) return rc;
+    return for_dtype(upd_dtype,
+                     [&](auto t) { return launch_median_window<decltype(t)>(out, updates, K, keep, P, st); });
 }
 
 

@@ -241,6 +241,37 @@ def trimmed_mean(out, updates, trim, stream=None):
     return out
 
 
+def median_window_mean(out, updates, keep, stream=None):
+    """Coordinate-wise mean of the values closest to the median on device (``fa_median_window_mean``,
+    Bulyan's second stage): per element, the K updates' values are sorted (-0 before +0, NaNs last), the
+    window of ``keep`` consecutive sorted values closest to their median is found (a tie keeps the lower
+    window) and averaged in ascending order. ``keep = K`` is :func:`trimmed_mean` at ``trim = 0`` bit for
+    bit.
+
+    out      flat device tensor of :func:`order_mean_dtype` of the updates' dtype (written)
+    updates  1 <= K <= 64 flat device tensors of one dtype and of ``out``'s length
+    keep     1 <= keep <= K
+    """
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_ORDER_K:
+        raise ValueError(f"median_window_mean takes 1..{MAX_ORDER_K} updates, got {K}")
+    P = out.numel()
+    dev = out.device
+    _check_dev("out", out, P, None)
+    upd_dt = updates[0].dtype
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one median_window_mean call must share a dtype")
+    with _on(dev):
+        st = _stream_handle(out, stream)
+        rc = lib.fa_median_window_mean(out.data_ptr(), fa_dtype(out), _abi.ptr_array([u.data_ptr() for u in updates]),
+                                       fa_dtype(upd_dt), K, int(keep), P, st)
+    _abi.check(rc)
+    return out
+
+
 def median(out, updates, stream=None):
     """Coordinate-wise median on device: :func:`trimmed_mean` with ``trim = (K - 1) // 2``
     (``np.median(S, 0)`` bit for bit)."""

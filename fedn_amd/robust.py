@@ -33,6 +33,11 @@ over the held updates that forms the new point in place and the K distances to i
 (``fa_centered_clip_step``, kernel ``k_cclip_dist``); the clipping coefficients of the next step come from
 the distances on the host (:func:`clip_coefficients`).
 
+Bulyan (El Mhamdi, Guerraoui and Rouault) joins the two kinds: ``bulyan(f)`` selects
+``theta = K - 2f`` updates by Krum iterated on the shrinking set (:func:`bulyan_select`, on the same K x K
+matrix) and averages, per coordinate, the ``theta - 2f`` of their values closest to their median
+(``fa_median_window_mean``, kernel ``k_median_window``).
+
 All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
 ``ops.MAX_ORDER_K`` (64) updates per round.
 
@@ -116,6 +121,40 @@ def krum_select(D, f, m):
     return sorted(int(i) for i in order[:m])
 
 
+def bulyan_f(byzantine_fraction, K):
+    """Byzantine clients Bulyan assumes among K: ``floor(byzantine_fraction * K)``, never more than the
+    paper's condition ``K >= 4f + 3`` allows (``(K - 3) // 4``); 0 below K = 3."""
+    if K < 3:
+        return 0
+    return max(0, min(math.floor(byzantine_fraction * K), (K - 3) // 4))
+
+
+def bulyan_select(D, f):
+    """Bulyan's selection: Krum iterated ``theta = K - 2f`` times on the shrinking set of clients of the
+    K x K squared-distance matrix ``D``. Each iteration takes :func:`krum_scores` of the remaining clients'
+    sub-matrix, picks the one with the smallest score (ties to the lower FIFO index) and removes it.
+    Returns ``(selected, pick_order, pick_scores)``: the picked FIFO indices ascending, in pick order, and
+    each pick's score at its iteration. Raises ``ValueError`` when a pick's score is not finite: nothing
+    trustworthy is left."""
+    D = np.array(D, dtype=np.float64)
+    if D.ndim != 2 or D.shape[0] != D.shape[1] or D.shape[0] < 1:
+        raise ValueError(f"a square distance matrix is needed, got shape {D.shape}")
+    K = D.shape[0]
+    theta = K - 2 * f
+    if f < 0 or (f > 0 and K < 4 * f + 3):
+        raise ValueError(f"f={f} of K={K} clients: Bulyan needs K >= 4f + 3")
+    left = list(range(K))
+    order, scores = [], []
+    for _ in range(theta):
+        sc = krum_scores(D[np.ix_(left, left)], f)
+        best = int(np.argmin(sc))                      # the first of equal scores: the lower FIFO index
+        if not np.isfinite(sc[best]):
+            raise ValueError(f"after {len(order)} of {theta} picks no remaining client has a finite Krum score")
+        order.append(left.pop(best))
+        scores.append(float(sc[best]))
+    return sorted(order), order, scores
+
+
 def weiszfeld_weights(d, nu):
     """The weights of one smoothed Weiszfeld step from the K squared distances ``d`` to the current
     point, in float64: ``w_k = 1 / max(nu, sqrt(d_k))`` where ``d_k`` is finite, else 0; the sum is taken
@@ -186,6 +225,7 @@ class RobustPipeline:
         self.host_side = 0           # updates the budget (or a full HBM) left on the host
         self._h2d, self._kern = [], []
         self.selected, self.scores = None, None     # select_mean: FIFO indices, float64 scores
+        self.pick_order = None                      # bulyan: the selected FIFO indices in pick order
         self.weights, self.distances = None, None   # geometric_median: the last pass's beta, sqrt(d)
         self.excluded, self.trace = [], []          # ... clients shut out as non-finite; (beta, d) per pass
         self.coefficients = None                    # centered_clip: the last pass's clipping coefficients
@@ -309,6 +349,29 @@ class RobustPipeline:
             self.scores = krum_scores(Dh, f)
             self.selected = krum_select(Dh, f, m)
             return {dt: self._reduce_group(dt, 0, self.selected) for dt in self.layout.groups}
+
+        return self._round(body)
+
+    def bulyan(self, f):
+        """Bulyan (El Mhamdi, Guerraoui and Rouault, 2018) with ``f`` assumed Byzantine
+        clients, ``K >= 4f + 3``: :func:`bulyan_select` picks ``theta = K - 2f`` updates by iterated Krum,
+        and per coordinate the ``beta = theta - 2f`` of their values closest to their median are averaged
+        (``ops.median_window_mean``, kernel ``k_median_window``). Host arrays like :meth:`result`'s;
+        ``self.selected`` (FIFO indices, ascending), ``self.pick_order`` and ``self.scores`` (each pick's
+        score, in pick order) stay on the pipeline.
+
+        The frame is :meth:`select_mean`'s: one pass for the K x K distance matrix, the selection on the
+        host in float64, one reduction over the selected updates — those on the host uploaded a second
+        time through the ring. Raises ``ValueError`` when a pick has no finite score."""
+        K = self._clients()
+        if f < 0 or (f > 0 and K < 4 * f + 3):
+            raise ValueError(f"f={f} of {K} updates: Bulyan needs K >= 4f + 3")
+
+        def body():
+            Dh = self._distance_matrix(K)
+            self.selected, self.pick_order, self.scores = bulyan_select(Dh, f)
+            keep = len(self.selected) - 2 * f
+            return {dt: self._reduce_group(dt, 0, self.selected, keep) for dt in self.layout.groups}
 
         return self._round(body)
 
@@ -518,9 +581,10 @@ class RobustPipeline:
         return [(np.ascontiguousarray(arrays[i]).reshape(-1), off) for i, off in self.layout.members[dt]
                 if self.layout.sizes[i]]
 
-    def _reduce_group(self, dt, trim, subset=None):
+    def _reduce_group(self, dt, trim, subset=None, keep=None):
         """Group ``dt`` of the trimmed mean over the held updates — all of them, or those at the FIFO
-        indices ``subset`` — as a pinned host tensor."""
+        indices ``subset`` — as a pinned host tensor. With ``keep`` the rule is the mean of the ``keep``
+        values closest to the median instead (``ops.median_window_mean``; ``trim`` plays no part)."""
         n = self.layout.group_elems[dt]
         odt = self._out_dt[dt]
         host = torch.empty(n, dtype=odt, pin_memory=True)
@@ -531,7 +595,10 @@ class RobustPipeline:
         def launch(b, lo, hi, views, step):
             if b not in outs:
                 outs[b] = torch.empty(step, dtype=odt, device=self.device)
-            ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
+            if keep is None:
+                ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
+            else:
+                ops.median_window_mean(outs[b][:hi - lo], views, keep, stream=self.compute)
 
         def after(b, lo, hi):
             # the result leaves on the compute stream: in order behind its launch and ahead of the

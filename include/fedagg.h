@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 12
+#define FA_ABI_VERSION 13
 
 /* element type codes */
 enum fa_dtype {
@@ -480,6 +480,31 @@ int64_t fa_centered_clip_work(int K, int64_t P);
 int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* dist, const void* const* updates,
                           int upd_dtype, const double* coef, int K, int64_t P, int accumulate, double* work,
                           void* stream);
+
+/*
+ * fa_median_window_mean (ABI 13): per element, the mean of the `keep` values closest to the median of K
+ * client updates — the second stage of Bulyan (El Mhamdi, Guerraoui and Rouault, 2018), which calls it
+ * with the theta = K_round - 2f selected updates and keep = theta - 2f. UNWEIGHTED like fa_trimmed_mean,
+ * whose total order, dtype pairs, accumulator type A and output rounding it shares. Per element:
+ *   1. the K values are sorted in fa_trimmed_mean's total order (-0 before +0, every NaN after +inf, all
+ *      NaNs equal): s[0 .. K-1];
+ *   2. med is the median KEPT IN A: A(s[(K-1)/2]) for an odd K, (A(s[K/2-1]) + A(s[K/2])) / A(2) for an
+ *      even one (one add, one IEEE division, each rounded once; not rounded to out_dtype);
+ *   3. the window start: a = 0; while a < K - keep and (A(s[a+keep]) - med) < (med - A(s[a])): a += 1.
+ *      Each difference is rounded once in A; the comparison is strict (a tie keeps the lower window) and
+ *      false when a NaN is involved (the walk stops). The predicate is monotone in a, so a is also the
+ *      number of j in [0, K - keep) for which it holds: the kernel counts;
+ *   4. out = (((A(s[a]) + A(s[a+1])) + ...) + A(s[a+keep-1])) / A(keep): ascending, starting from A(s[a]),
+ *      every add rounded once, no FMA, one IEEE division, one rounding to out_dtype.
+ * With keep = K this is fa_trimmed_mean at trim 0, bit for bit.
+ *
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * keep     the window length, 1 <= keep <= K (K - keep may be odd)
+ * FA_EINVAL: a null pointer, K or keep out of range, P < 0; FA_EDTYPE: a dtype pair fa_trimmed_mean does
+ * not take; FA_OK for P = 0 — all before any HIP call. fa_last_kernel reports "k_median_window".
+ */
+int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype,
+                          int K, int keep, int64_t P, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,379 @@
+"""Bulyan on the GPU: ``fa_median_window_mean`` (kernel ``k_median_window``) through
+``ops.median_window_mean``, ``robust.RobustPipeline.bulyan`` and the ``bulyan`` plug-in, against the oracle
+tests/bulyan_ref.py: bit for bit at every dtype, K, window length, alignment and tail, the same bits on
+every call, selections equal."""
+import numpy as np
+import pytest
+import torch
+
+import bulyan_ref as br
+import krum_ref as kr
+from golden_io import assert_lists_identical
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+KS = [1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 63, 64]        # every KP, K = KP, K = KP + 1, padding at its most
+PS = [1, 5, 257, 4099]
+ROW = 4160                                                 # >= 1 + max(PS); rows of a (K, ROW) matrix stay 16-B aligned
+DTYPES = ["f32", "f64", "f16", "bf16", "i32", "i64"]
+NP_DT = {"f32": np.float32, "f64": np.float64, "f16": np.float16, "bf16": np.float32, "i32": np.int32, "i64": np.int64}
+TORCH_DT = {"f32": torch.float32, "f64": torch.float64, "f16": torch.float16, "bf16": torch.bfloat16,
+            "i32": torch.int32, "i64": torch.int64}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a HIP device")
+    from fedn_amd import _abi
+    _abi.load()
+    yield
+    torch.cuda.synchronize()
+
+
+def _bf16_exact(x):
+    return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def _keeps(K):
+    fmax = (K - 3) // 4 if K >= 3 else 0
+    return sorted({1, 2, K - 2, K - 1, K, K - 2 * fmax} & set(range(1, K + 1)))
+
+
+def _plant(S, c, name, rng):
+    """Planted columns from column ``c`` on; returns the next free column."""
+    K = S.shape[0]
+    dt = S.dtype
+    half, third = K // 2, max(1, K // 3)
+    cols = []
+    cols.append(np.full(K, S[0, c]))                                           # all values equal
+    dup = S[:, c + 1].copy()
+    dup[np.argsort(dup)[K // 4:K // 4 + half + 1]] = np.sort(dup)[K // 2]      # a run of duplicates around the median
+    cols.append(dup)
+    two = S[:, c + 2].copy()
+    two[rng.permutation(K)[:half]] = two[0]                                    # two runs of duplicates
+    cols.append(two)
+    if dt.kind == "f":
+        z = np.where(rng.random(K) < 0.5, -0.0, 0.0)                           # -0 and +0 mixed
+        cols.append(z)
+        z2 = S[:, c + 3].copy()
+        z2[rng.permutation(K)[:half + 1]] = -0.0
+        z2[rng.permutation(K)[:third]] = 0.0
+        cols.append(z2)
+        for lo, hi in ((1, 0), (0, 1), (1, 1), (half + 1, 0), (0, half + 1)):  # +-inf: a few, a majority
+            v = S[:, c + 4].copy()
+            p = rng.permutation(K)
+            v[p[:lo]] = -np.inf
+            v[p[lo:lo + hi]] = np.inf
+            cols.append(v)
+        for n in (min(third, (K - 1) // 2), half + 1, K):                      # NaNs: a minority, a majority, all
+            v = S[:, c + 5].copy()
+            v[rng.permutation(K)[:n]] = np.nan
+            cols.append(v)
+        v = S[:, c + 6].copy()
+        v[rng.permutation(K)[:third]] = np.nan
+        v[rng.permutation(K)[:third]] = np.inf
+        cols.append(v)
+        if name == "f16":                                                      # an f32 mean that rounds in the conversion
+            cols.append(1.0 + rng.integers(0, 7, K) * 2.0 ** -10)
+            cols.append(np.full(K, 65504.0))                                   # the f32 sum is past f16's range, the mean is not
+            cols.append(rng.choice([6.0e-8, 1.2e-7, 6.1e-5], K))               # subnormal results
+    else:
+        info = np.iinfo(dt)
+        v = S[:, c + 3].copy()
+        v[rng.permutation(K)[:third]] = info.min
+        v[rng.permutation(K)[:third]] = info.max
+        cols.append(v)
+        if name == "i64":                                                      # not exact in float64
+            cols.append(2 ** 53 + 2 * rng.integers(1, 500, K) + 1)
+            cols.append(-(2 ** 53) - rng.integers(1, 1000, K))
+            cols.append((2 ** 62 + rng.integers(1, 1000, K)) * rng.choice([-1, 1], K))
+    for i, v in enumerate(cols):
+        S[:, c + i] = np.asarray(v).astype(dt)
+    return c + len(cols)
+
+
+def _data(rng, name, K):
+    """K updates that are close to each other, as in federated learning — a base plus small noise — with
+    the planted columns at the start (P = 1, 5 see some), past one lane's strip and at the ragged end."""
+    dt = np.dtype(NP_DT[name])
+    x = rng.standard_normal(ROW) + 0.05 * rng.standard_normal((K, ROW))
+    if dt.kind == "i":
+        x = np.round(x * (2.0 ** 20 if name == "i32" else 2.0 ** 40))
+    S = np.ascontiguousarray(x.astype(dt))
+    for c in (0, 40, 230, 4070):
+        end = _plant(S, c, name, rng)
+        assert end <= c + 27
+    return _bf16_exact(S) if name == "bf16" else S
+
+
+def _upload(S, name):
+    t = torch.from_numpy(np.ascontiguousarray(S)).to(DEV)
+    return t.to(torch.bfloat16) if name == "bf16" else t       # exact: the values are bf16's
+
+
+def _assert_bits(got, want, what):
+    assert_lists_identical([got], [want], what)
+
+
+# ---- ops level ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", KS)
+@pytest.mark.parametrize("name", DTYPES)
+def test_ops_median_window_mean(name, K):
+    """Every window length of interest at every size, on 16-B aligned buffers (the vector path with its
+    ragged tail) and on buffers one element past a 16-B boundary (E = 1), bit for bit against the oracle;
+    keep = K against ops.trimmed_mean on the same buffers; two calls give the same bits."""
+    from fedn_amd import ops
+    rng = np.random.default_rng(1000 * DTYPES.index(name) + K)
+    S = _data(rng, name, K)
+    dev = _upload(S, name)
+    odt = ops.order_mean_dtype(TORCH_DT[name])
+    s = br.rr.sorted_values(S)                                 # sorted once for every keep
+    for keep in _keeps(K):
+        want = br.window_mean_of_sorted(s, keep)
+        for P in PS:
+            for off in (0, 1):
+                views = [dev[k, off:off + P] for k in range(K)]
+                assert all((v.data_ptr() % 16 != 0) == bool(off) for v in views)
+                out = torch.empty(P, dtype=odt, device=DEV)
+                assert ops.median_window_mean(out, views, keep) is out
+                assert ops.last_kernel() == "k_median_window"
+                got = out.cpu().numpy()
+                _assert_bits(got, want[off:off + P], f"{name} K={K} keep={keep} P={P} off={off}")
+                again = torch.empty(P, dtype=odt, device=DEV)
+                ops.median_window_mean(again, views, keep)
+                assert torch.equal(again.view(torch.uint8), out.view(torch.uint8)), "two calls differ"
+                if keep == K:
+                    tm = torch.empty(P, dtype=odt, device=DEV)
+                    ops.trimmed_mean(tm, views, 0)
+                    assert torch.equal(tm.view(torch.uint8), out.view(torch.uint8)), "keep = K is the trimmed mean at trim 0"
+
+
+@pytest.mark.parametrize("name", ["f32", "f64", "i32"])
+def test_nothing_outside_the_window_is_written(name):
+    from fedn_amd import ops
+    K, keep, guard = 9, 5, 64
+    S = _data(np.random.default_rng(3), name, K)
+    dev = _upload(S, name)
+    odt = ops.order_mean_dtype(TORCH_DT[name])
+    want = br.window_mean(S, keep)
+    for P in (5, 257, 4099):
+        for off in (0, 1):
+            buf = torch.full((guard + off + P + guard,), -5.0, dtype=odt, device=DEV)
+            ops.median_window_mean(buf[guard + off:guard + off + P], [dev[k, :P] for k in range(K)], keep)
+            o = buf.cpu().numpy()
+            assert (o[:guard + off] == -5).all() and (o[guard + off + P:] == -5).all(), (name, P, off)
+            _assert_bits(o[guard + off:guard + off + P], want[:P], f"{name} P={P} off={off}")
+    assert torch.equal(dev.view(torch.uint8), _upload(S, name).view(torch.uint8)), "the updates are read only"
+
+
+def test_ops_refuses_bad_arguments():
+    from fedn_amd import _abi, ops
+    x = torch.zeros(8, device=DEV)
+    out = torch.zeros(8, device=DEV)
+    with pytest.raises(ValueError):
+        ops.median_window_mean(out, [], 1)
+    with pytest.raises(ValueError):
+        ops.median_window_mean(out, [x] * 65, 1)
+    with pytest.raises(ValueError):
+        ops.median_window_mean(out, [x, torch.zeros(9, device=DEV)], 1)                       # lengths differ
+    with pytest.raises(TypeError):
+        ops.median_window_mean(out, [x, torch.zeros(8, dtype=torch.float64, device=DEV)], 1)  # dtypes differ
+    for keep in (0, 3, -1):
+        with pytest.raises(_abi.FedAggError) as e:
+            ops.median_window_mean(out, [x, x], keep)
+        assert e.value.status == _abi.FA_EINVAL
+    with pytest.raises(_abi.FedAggError) as e:
+        ops.median_window_mean(torch.zeros(8, dtype=torch.float64, device=DEV), [x, x], 1)    # not f32's output dtype
+    assert e.value.status == _abi.FA_EDTYPE
+
+
+# ---- rounds ------------------------------------------------------------------------------------------
+SPEC = [((300, 50), np.float32), ((77,), np.int64), ((0,), np.float32), ((1001,), np.float64), ((), np.float32),
+        ((513,), np.float16)]
+
+
+def _round_updates(seed, K, f, spec):
+    """K updates of the model ``spec`` ([(shape, dtype)]): honest ones are base + sigma_k * noise with
+    graded sigma_k = 0.05 * (1 + 0.25 * rank) in shuffled order (so the scores are separated at every
+    iteration of the selection); the f hostile ones take honest clients' places as a sign flip, large noise
+    and one NaN. Integer tensors hold round(1000 * value). Returns (updates, hostile indices)."""
+    rng = np.random.default_rng(seed)
+    sigma = 0.05 * (1 + 0.25 * rng.permutation(K))
+    hostile = sorted(int(i) for i in rng.choice(K, size=f, replace=False))
+    base = [rng.standard_normal(s) for s, _ in spec]
+    ups = []
+    for k in range(K):
+        kind = hostile.index(k) % 3 if k in hostile else None
+        u = []
+        for b, (s, dt) in zip(base, spec):
+            v = b + sigma[k] * rng.standard_normal(s)
+            if kind == 0:
+                v = -v
+            elif kind == 1:
+                v = b + 5.0 * rng.standard_normal(s)
+            if np.dtype(dt).kind == "i":
+                v = np.round(1000.0 * v)
+            v = np.asarray(v, dtype=dt).reshape(s)
+            if kind == 2 and np.dtype(dt).kind == "f" and v.size:
+                v.reshape(-1)[v.size // 2] = np.nan
+            u.append(v)
+        ups.append(u)
+    return ups, hostile
+
+
+def _selection(ups, f, what):
+    """The oracle's selection from the oracle's distances, after asserting the precondition in float64 on
+    the CPU: at EVERY iteration the relative gap between the smallest score and the next one is at least
+    10 x the distance bound, so the kernel's rounding cannot change a pick. One exact tie is structural
+    and skipped over: late iterations have nn = 1, a score is then the nearest neighbour's distance, and
+    two mutual nearest neighbours hold the SAME entry of the exactly symmetric D — equal on the device as
+    here, whatever its rounding, and broken by the FIFO index in both."""
+    from fedn_amd import ops
+    D = kr.model_distances(ups)
+    bound = 10 * max(ops.sqdist_rtol(np.asarray(a).dtype, np.asarray(a).size) for a in ups[0])
+    left = list(range(len(ups)))
+    worst = np.inf
+    for _ in range(len(ups) - 2 * f):
+        n = len(left)
+        sc = kr.scores(D[np.ix_(left, left)].tolist(), f)
+        order = sorted(range(n), key=lambda i: sc[i])
+        nxt = 1
+        if n > 2 and max(n - f - 2, 1) == 1 and sc[order[1]] == sc[order[0]] == D[left[order[0]], left[order[1]]]:
+            nxt = 2                                            # mutual nearest neighbours
+        if nxt < n and np.isfinite(sc[order[nxt]]):
+            worst = min(worst, (sc[order[nxt]] - sc[order[0]]) / sc[order[nxt]])
+        left.pop(order[0])
+    print(f"{what}: smallest score gap {worst:.3e}, needed {bound:.2e}")
+    assert worst >= bound, f"{what}: precondition — score gap {worst:.3e} below {bound:.2e}: pick another seed"
+    return br.select(D.tolist(), f)
+
+
+# seeds whose score gaps pass _selection's precondition: found on the CPU with the oracle alone
+PIPE_SEEDS = {7: 0, 11: 0, 23: 0}
+
+
+@pytest.mark.parametrize("K", [7, 11, 23])
+def test_pipeline_hbm_and_ring(K, monkeypatch):
+    """The largest legal f. Every update in HBM (one launch per dtype group), then the same round with a
+    zero budget: every update stays on the host and both passes walk the groups slice by slice through the
+    ring (the f32 group takes four slices). Same selection, same bits, the oracle's."""
+    from fedn_amd import robust
+    from fedn_amd.budget import HbmBudget
+    f = (K - 3) // 4
+    ups, hostile = _round_updates(PIPE_SEEDS[K], K, f, SPEC)
+    want_sel, want_order, want_scores = _selection(ups, f, f"pipeline K={K}")
+    want, sel2 = br.combine(ups, f)
+    assert sel2 == want_sel and len(want_sel) == K - 2 * f
+    monkeypatch.setattr(robust, "SLICE_BYTES", 16384)
+    models = []
+    for limit, host_side in ((None, 0), (0, K)):
+        pipe = robust.RobustPipeline(DEV, ups[0], budget=HbmBudget(limit=limit) if limit is not None else None)
+        try:
+            for u in ups[1:]:
+                pipe.add(u)
+            assert pipe.host_side == host_side
+            model = pipe.bulyan(f)
+            assert pipe.selected == want_sel and pipe.pick_order == want_order, (pipe.selected, pipe.pick_order)
+            assert np.allclose(pipe.scores, want_scores, rtol=1e-3, atol=0)
+        finally:
+            pipe.release()
+        assert_lists_identical(model, want, f"K={K} host_side={host_side} vs oracle")
+        models.append(model)
+    assert_lists_identical(models[0], models[1], "HBM vs ring")
+    assert [a.dtype for a in models[0]] == [np.dtype(d) for d in (np.float32, np.float64, np.float32, np.float64,
+                                                                np.float32, np.float16)]
+    assert models[0][2].shape == (0,)
+
+
+def test_pipeline_refuses_bad_f():
+    from fedn_amd import robust
+    ups, _ = _round_updates(0, 7, 0, [((33,), np.float32)])
+    pipe = robust.RobustPipeline(DEV, ups[0])
+    try:
+        for u in ups[1:]:
+            pipe.add(u)
+        for f in (-1, 2):                                      # 7 < 4 * 2 + 3
+            with pytest.raises(ValueError):
+                pipe.bulyan(f)
+        model = pipe.bulyan(0)                                 # f = 0: everyone, the plain mean
+        assert pipe.selected == list(range(7))
+        assert_lists_identical(model, br.rr.combine(ups, 0), "f = 0")
+    finally:
+        pipe.release()
+
+
+def _run_round(ups, parameters=None, delete_models=True):
+    from fedn_amd.aggregators import get_aggregator
+    from fedn_amd.updatehandler import MemoryUpdateHandler
+    uh = MemoryUpdateHandler()
+    agg = get_aggregator("bulyan", uh)
+    agg.device = torch.device(DEV)
+    mus = [uh.submit(u, 10 + k) for k, u in enumerate(ups)]
+    model, data = agg.combine_models(helper=None, delete_models=delete_models, parameters=parameters)
+    return model, data, uh, mus, agg
+
+
+def _attack_round():
+    """K = 11, f = 2: nine honest clients, client 3 at 1e30 everywhere, client 8 all NaN."""
+    spec = [((4099,), np.float32), ((257,), np.float64)]
+    ups, _ = _round_updates(1, 11, 0, spec)
+    for i, (s, dt) in enumerate(spec):
+        ups[3][i] = np.full(s, 1e30, dtype=dt)
+        ups[8][i] = np.full(s, np.nan, dtype=dt)
+    return ups, [3, 8]
+
+
+def test_plugin_attack_round():
+    ups, hostile = _attack_round()
+    f = br.byzantine_count(0.2, 11)
+    assert f == 2
+    want_sel, want_order, _ = _selection(ups, f, "attack round")
+    want, _ = br.combine(ups, f)
+    honest = [k for k in range(11) if k not in hostile]
+    for i, w in enumerate(want):                               # a property of this input: checked on the oracle first
+        H = np.stack([ups[k][i] for k in honest])
+        assert np.isfinite(w).all() and (w >= H.min(axis=0)).all() and (w <= H.max(axis=0)).all()
+    assert not set(want_sel) & set(hostile)
+    model, data, uh, _, agg = _run_round(ups, {"byzantine_fraction": 0.2})
+    assert data["nr_aggregated_models"] == 11
+    for key in ("time_model_load", "time_model_aggregation", "time_h2d", "time_kernel", "time_pack", "time_d2h"):
+        assert key in data
+    assert agg.selected == want_sel and agg.pick_order == want_order and len(agg.scores) == 7
+    assert not set(agg.selected) & set(hostile), "no hostile client is selected"
+    assert_lists_identical(model, want, "attack round")
+    assert all(np.isfinite(a).all() for a in model)
+    assert uh.model_updates.qsize() == 0 and not uh.store.models, "every update is deleted once the result exists"
+
+
+def test_plugin_default_fraction_and_kept_models():
+    """No parameters: byzantine_fraction = 0.2; delete_models = False keeps every update in storage."""
+    ups, hostile = _attack_round()
+    want, want_sel = br.combine(ups, 2)
+    model, data, uh, mus, agg = _run_round(ups, None, delete_models=False)
+    assert data["nr_aggregated_models"] == 11 and agg.selected == want_sel
+    assert_lists_identical(model, want, "default fraction")
+    assert set(uh.store.models) == {mu.model_update_id for mu in mus}
+
+
+def test_too_few_finite_scores_keeps_every_update():
+    """K = 7, f = 1: theta = 5 picks, but three clients hold NaNs — no remaining client has K - f - 2 = 4
+    finite neighbours: (None, data), nothing deleted."""
+    ups, _ = _round_updates(5, 7, 0, [((257,), np.float32)])
+    for k in (0, 3, 5):
+        ups[k][0][7] = np.nan
+    with pytest.raises(ValueError):
+        br.select(kr.model_distances(ups).tolist(), 1)
+    model, data, uh, mus, agg = _run_round(ups, {"byzantine_fraction": 0.2})
+    assert model is None and data["nr_aggregated_models"] == 0 and agg.selected is None
+    assert uh.model_updates.qsize() == 0
+    assert set(uh.store.models) == {mu.model_update_id for mu in mus}
+
+
+def test_more_than_64_updates_refused():
+    ups, _ = _round_updates(12, 65, 0, [((33,), np.float32)])
+    model, data, uh, mus, _ = _run_round(ups)
+    assert model is None and data["nr_aggregated_models"] == 0
+    assert uh.model_updates.qsize() == 0
+    assert set(uh.store.models) == {m.model_update_id for m in mus}, "nothing is deleted"

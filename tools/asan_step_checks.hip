@@ -6,7 +6,7 @@
 //         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Xarch_host -fno-omit-frame-pointer -o /tmp/step_checks asan_step_checks.hip
 //     ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 /tmp/step_checks
-// profiles/r17_hostfold_asan_host.log is its output.
+// profiles/r18_bulyan_asan_host.log is its output (r17_hostfold_asan_host.log: before fa_median_window_mean).
 #include "../fedn_amd/csrc/fedagg.hip"
 
 #include <cstdlib>
@@ -90,6 +90,25 @@ int main() {
     expect("wmean accumulate, P=0 (null updates pass)",
            fa_weighted_mean_sqdist(nullptr, FA_F64, dist, ups, FA_I64, beta, K, 0, 1, work, nullptr), FA_OK, nullptr);
     expect("trimmed mean P=0", fa_trimmed_mean(out, FA_F32, ups, FA_BF16, K, 1, 0, nullptr), FA_OK, nullptr);
+    expect("median window null out", fa_median_window_mean(nullptr, FA_F32, ups, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: null pointer argument");
+    expect("median window null updates", fa_median_window_mean(out, FA_F32, nullptr, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: null pointer argument");
+    expect("median window K=0", fa_median_window_mean(out, FA_F32, ups, FA_F32, 0, 1, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: K=0 outside 1..64");
+    expect("median window K=65", fa_median_window_mean(out, FA_F32, ups, FA_F32, 65, 1, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: K=65 outside 1..64");
+    expect("median window keep=0", fa_median_window_mean(out, FA_F32, ups, FA_F32, K, 0, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: keep=0 outside 1..K=5");
+    expect("median window keep=K+1", fa_median_window_mean(out, FA_F32, ups, FA_F32, K, K + 1, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: keep=6 outside 1..K=5");
+    expect("median window P<0", fa_median_window_mean(out, FA_F32, ups, FA_F32, K, 3, -1, nullptr), FA_EINVAL,
+           "fa_median_window_mean: negative size (P=-1)");
+    expect("median window dtype pair", fa_median_window_mean(out, FA_F64, ups, FA_F32, K, 3, 64, nullptr), FA_EDTYPE,
+           "fa_median_window_mean: unsupported dtype pair (update 0, output 1)");
+    expect("median window updates[4] null", fa_median_window_mean(out, FA_F32, ups, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
+           "fa_median_window_mean: updates[4] is NULL");
+    expect("median window P=0", fa_median_window_mean(out, FA_F64, ups, FA_I64, K, K, 0, nullptr), FA_OK, nullptr);
     // P = 0 without accumulate reaches the launchers (table builder, geometry, nwg = 0); with no device the
     // finish launch reports a HIP error: either status is fine, a sanitizer report is not
     int rc = fa_weighted_mean_sqdist(nullptr, FA_F32, dist, ups, FA_F32, beta, K, 0, 0, work, nullptr);
