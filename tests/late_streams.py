@@ -13,7 +13,8 @@ import torch
 
 DEV = "cuda:0"
 SPIN_CYCLES = 30_000_000              # torch.cuda._sleep cycles: ~10 ms or more (the poison test's spin)
-LATE_OPS = ("trimmed_mean", "pairwise_sqdist", "weighted_mean_sqdist", "centered_clip_step")
+LATE_OPS = ("trimmed_mean", "pairwise_sqdist", "weighted_mean_sqdist", "centered_clip_step",
+            "median_window_mean")
 
 
 def side_by_side_streams():

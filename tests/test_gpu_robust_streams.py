@@ -108,6 +108,11 @@ def _warm():
             pipe = _pipeline(rule, None, None, _budget(True))
             _check_oracle(rule, *_reduce(pipe, rule), f"{rule}, undelayed")
             pipe.release()
+        # Bulyan's window kernel (test_ops_on_a_late_side_stream; its late rounds are test_gpu_bulyan_streams.py's):
+        # at K = 6 its f is 0, the window is every value and the model the plain mean
+        pipe = _pipeline("trimmed", None, None, _budget(True))
+        assert_lists_identical(pipe.bulyan(0), _case().trim[0], "bulyan at f = 0, undelayed")
+        pipe.release()
     torch.cuda.synchronize()
 
 
@@ -412,7 +417,7 @@ def test_fresh_hbm_after_queued_work(alloc, where, budgeted, monkeypatch):
 # ---- ops level: stream= ------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", LATE_OPS)
 def test_ops_on_a_late_side_stream(name):
-    """Each of the four ops with ``stream=`` a side stream that spins first, against the same call on the
+    """Each of the five ops with ``stream=`` a side stream that spins first, against the same call on the
     current stream: the same bits; the outputs still hold their sentinel and the event behind the op is
     still pending when a marker on the current stream has completed (the op neither ran on nor waited for
     the current stream); and blocks of the op's scratch size (``fa_*_work``) churned on the current stream
@@ -430,7 +435,8 @@ def test_ops_on_a_late_side_stream(name):
         coef = rng.uniform(0.05, 1.0, K).tolist()
 
         def outputs():
-            shapes = {"trimmed_mean": [(P, torch.float32)], "pairwise_sqdist": [(K * K, torch.float64)],
+            shapes = {"trimmed_mean": [(P, torch.float32)], "median_window_mean": [(P, torch.float32)],
+                      "pairwise_sqdist": [(K * K, torch.float64)],
                       "weighted_mean_sqdist": [(P, torch.float32), (K, torch.float64)],
                       "centered_clip_step": [(P, torch.float32), (K, torch.float64)]}[name]
             return [torch.full((n,), -7.0, dtype=dt, device=DEV) for n, dt in shapes]
@@ -438,6 +444,8 @@ def test_ops_on_a_late_side_stream(name):
         def call(outs, stream):
             if name == "trimmed_mean":
                 ops.trimmed_mean(outs[0], views, 1, stream=stream)
+            elif name == "median_window_mean":
+                ops.median_window_mean(outs[0], views, 4, stream=stream)
             elif name == "pairwise_sqdist":
                 ops.pairwise_sqdist(views, out=outs[0].view(K, K), stream=stream)
             elif name == "weighted_mean_sqdist":
@@ -445,7 +453,7 @@ def test_ops_on_a_late_side_stream(name):
             else:
                 ops.centered_clip_step(views, centre, coef, out=outs[0], dist=outs[1], stream=stream)
 
-        work = {"trimmed_mean": 0, "pairwise_sqdist": int(lib.fa_pairwise_sqdist_work(K, P)),
+        work = {"trimmed_mean": 0, "median_window_mean": 0, "pairwise_sqdist": int(lib.fa_pairwise_sqdist_work(K, P)),
                 "weighted_mean_sqdist": int(lib.fa_wmean_sqdist_work(K, P)),
                 "centered_clip_step": int(lib.fa_centered_clip_work(K, P))}[name]
         want = outputs()
