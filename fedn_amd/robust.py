@@ -7,7 +7,9 @@ rest averaged (``fa_trimmed_mean``, kernel ``k_order_mean``). S
 round's updates — in HBM while ``budget.HbmBudget`` admits them, on the host otherwise — and
 ``result(trim)`` reduces them:
 
-  * every update in HBM: ONE launch per dtype group reads each update once and writes the model;
+  * every update in HBM: ONE launch per dtype group reads each update once and writes the model (the
+    two iterated rules below launch once per SLICE_BYTES of a group instead, on the updates in place:
+    their distance sums, which steer the next pass, then have the same bits wherever the updates sit);
   * some updates on the host: the groups are reduced slice by slice. A slice of each host-side update
     is copied into a reused device ring (one row per such update, two buffers) on the copy stream
     while the compute stream reduces the previous slice; updates in HBM are addressed in place at
@@ -381,7 +383,12 @@ class RobustPipeline:
         ``step(b, lo, hi, views, stride, acc, accumulate)`` launches one slice's op on the accumulator —
         written by the pass's first launch, added to by the rest — and ``after`` is :meth:`_walk_group`'s.
         With ``coef``, ``(coef, sums)`` is appended to ``trace``. Called inside :meth:`_round`: on the
-        compute stream, the staged updates' ``ready`` events already waited for."""
+        compute stream, the staged updates' ``ready`` events already waited for.
+
+        With ``coef`` — a pass of an iterated rule, whose sums become the next pass's weights — the groups
+        are walked at the slice bounds WHEREVER the updates sit: the sums are then added in one grouping,
+        the same bits whether the budget left updates on the host or not, and so is the model. (The
+        selection rules' matrix only has to order the scores: it keeps its one launch per group.)"""
         acc = torch.zeros(shape, dtype=torch.float64, device=self.device)
         written = False
         for dt in self.layout.groups:
@@ -394,7 +401,7 @@ class RobustPipeline:
                 step(b, lo, hi, views, stride, acc, written)
                 written = True
 
-            self._walk_group(dt, None, launch, after)
+            self._walk_group(dt, None, launch, after, sliced=coef is not None)
         tic = time.perf_counter()
         sums = acc.cpu().numpy()                     # (synchronises the compute stream)
         self.time_d2h += time.perf_counter() - tic
@@ -608,10 +615,11 @@ class RobustPipeline:
         self._walk_group(dt, subset, launch, after)
         return host
 
-    def _walk_group(self, dt, subset, launch, after):
+    def _walk_group(self, dt, subset, launch, after, sliced=False):
         """Run ``launch(b, lo, hi, views, step)`` over group ``dt`` of the updates at ``subset`` (all when
         None): once when they all sit in HBM, else slice by slice with the host-side ones copied through
-        the two-buffer ring; ``after(b, lo, hi)`` follows each launch's timing events.
+        the two-buffer ring; ``after(b, lo, hi)`` follows each launch's timing events. ``sliced`` walks
+        the slice bounds even when every update sits in HBM (no ring then: the views are the updates' own).
 
         Every view handed to ``launch`` starts on a 16-byte boundary, so the kernels take their 16-byte
         load paths: a staged update's group starts at a multiple of ``layout.ALIGN`` bytes, slices
@@ -621,7 +629,7 @@ class RobustPipeline:
         isz, goff = dt.itemsize, self.layout.group_byte_offset[dt]
         used = list(range(len(self.updates))) if subset is None else list(subset)
         on_host = [k for k in used if not isinstance(self.updates[k], StagedModel)]
-        if on_host:
+        if on_host or sliced:
             step = max(SLICE_ALIGN, SLICE_BYTES // isz // SLICE_ALIGN * SLICE_ALIGN)
         else:
             step = n                                 # every update in HBM: one launch

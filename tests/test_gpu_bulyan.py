@@ -11,6 +11,7 @@ import torch
 import bulyan_ref as br
 import krum_ref as kr
 from golden_io import assert_lists_identical
+from robust_fuzz_cases import bulyan_gap, round_updates, selection_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -222,32 +223,9 @@ SPEC = [((300, 50), np.float32), ((77,), np.int64), ((0,), np.float32), ((1001,)
 
 
 def _round_updates(seed, K, f, spec):
-    """K updates of the model ``spec`` ([(shape, dtype)]): honest ones are base + sigma_k * noise with
-    graded sigma_k = 0.05 * (1 + 0.25 * rank) in shuffled order (so the scores are separated at every
-    iteration of the selection); the f hostile ones take honest clients' places as a sign flip, large noise
-    and one NaN. Integer tensors hold round(1000 * value). Returns (updates, hostile indices)."""
-    rng = np.random.default_rng(seed)
-    sigma = 0.05 * (1 + 0.25 * rng.permutation(K))
-    hostile = sorted(int(i) for i in rng.choice(K, size=f, replace=False))
-    base = [rng.standard_normal(s) for s, _ in spec]
-    ups = []
-    for k in range(K):
-        kind = hostile.index(k) % 3 if k in hostile else None
-        u = []
-        for b, (s, dt) in zip(base, spec):
-            v = b + sigma[k] * rng.standard_normal(s)
-            if kind == 0:
-                v = -v
-            elif kind == 1:
-                v = b + 5.0 * rng.standard_normal(s)
-            if np.dtype(dt).kind == "i":
-                v = np.round(1000.0 * v)
-            v = np.asarray(v, dtype=dt).reshape(s)
-            if kind == 2 and np.dtype(dt).kind == "f" and v.size:
-                v.reshape(-1)[v.size // 2] = np.nan
-            u.append(v)
-        ups.append(u)
-    return ups, hostile
+    """K updates of the model ``spec``, f of them hostile: the generator the robust rules' tests share
+    (tests/robust_fuzz_cases.round_updates). Returns (updates, hostile indices)."""
+    return round_updates(seed, K, f, spec)
 
 
 def _selection(ups, f, what):
@@ -256,22 +234,11 @@ def _selection(ups, f, what):
     10 x the distance bound, so the kernel's rounding cannot change a pick. One exact tie is structural
     and skipped over: late iterations have nn = 1, a score is then the nearest neighbour's distance, and
     two mutual nearest neighbours hold the SAME entry of the exactly symmetric D — equal on the device as
-    here, whatever its rounding, and broken by the FIFO index in both."""
-    from fedn_amd import ops
+    here, whatever its rounding, and broken by the FIFO index in both (tests/robust_fuzz_cases.bulyan_gap,
+    which the fuzz shares)."""
     D = kr.model_distances(ups)
-    bound = 10 * max(ops.sqdist_rtol(np.asarray(a).dtype, np.asarray(a).size) for a in ups[0])
-    left = list(range(len(ups)))
-    worst = np.inf
-    for _ in range(len(ups) - 2 * f):
-        n = len(left)
-        sc = kr.scores(D[np.ix_(left, left)].tolist(), f)
-        order = sorted(range(n), key=lambda i: sc[i])
-        nxt = 1
-        if n > 2 and max(n - f - 2, 1) == 1 and sc[order[1]] == sc[order[0]] == D[left[order[0]], left[order[1]]]:
-            nxt = 2                                            # mutual nearest neighbours
-        if nxt < n and np.isfinite(sc[order[nxt]]):
-            worst = min(worst, (sc[order[nxt]] - sc[order[0]]) / sc[order[nxt]])
-        left.pop(order[0])
+    bound = selection_bound(ups)
+    worst = bulyan_gap(D, f)
     print(f"{what}: smallest score gap {worst:.3e}, needed {bound:.2e}")
     assert worst >= bound, f"{what}: precondition — score gap {worst:.3e} below {bound:.2e}: pick another seed"
     return br.select(D.tolist(), f)

@@ -15,6 +15,7 @@ from golden_io import assert_lists_identical
 from robust_checks import check_cclip_chain as _check_chain
 from robust_checks import nan_clients as _nan_clients
 from robust_checks import same_bits as _same_bits
+from robust_fuzz_cases import center_round_updates
 
 pytestmark = pytest.mark.gpu
 
@@ -472,41 +473,10 @@ def _byzantine_count(fraction, K):
 
 
 def _round_updates(seed, K, spec, fraction=FRACTION):
-    """K updates of the model ``spec`` ([(shape, dtype)]) and the global model they started from
-    (tests/test_gpu_geomed.py's generator, around a global model): the global model is ``base``; honest
-    updates are base + shift + sigma_k * noise with a common shift of scale 0.1 and graded
-    sigma_k = 0.05 * (1 + 0.25 * rank) in shuffled order; the f = byzantine_count hostile ones take honest
-    clients' places as a x10 sign flip of the step, noise of scale 5 and one NaN. Integer tensors hold
-    round(value). Returns (updates, hostile indices, global model)."""
-    rng = np.random.default_rng(seed)
-    f = _byzantine_count(fraction, K)
-    sigma = 0.05 * (1 + 0.25 * rng.permutation(K))
-    hostile = sorted(int(i) for i in rng.choice(K, size=f, replace=False))
-    base = [rng.standard_normal(s) for s, _ in spec]
-    shift = [0.1 * rng.standard_normal(s) for s, _ in spec]
-
-    def store(v, s, dt):
-        if np.dtype(dt).kind == "i":
-            v = np.round(v)
-        return np.asarray(v, dtype=dt).reshape(s)
-
-    center = [store(b, s, dt) for b, (s, dt) in zip(base, spec)]
-    ups = []
-    for k in range(K):
-        kind = hostile.index(k) % 3 if k in hostile else None
-        u = []
-        for b, sh, (s, dt) in zip(base, shift, spec):
-            step = sh + sigma[k] * rng.standard_normal(s)
-            if kind == 0:
-                step = -10.0 * step                              # x10 sign flip of the step
-            elif kind == 1:
-                step = 5.0 * rng.standard_normal(s)              # large noise
-            v = store(b + step, s, dt)
-            if kind == 2 and np.dtype(dt).kind == "f" and v.size:
-                v.reshape(-1)[v.size // 2] = np.nan              # one NaN
-            u.append(v)
-        ups.append(u)
-    return ups, hostile, center
+    """K updates of the model ``spec`` around the global model they started from, f = byzantine_count(fraction,
+    K) of them hostile: the generator the robust rules' tests share
+    (tests/robust_fuzz_cases.center_round_updates). Returns (updates, hostile indices, global model)."""
+    return center_round_updates(seed, K, _byzantine_count(fraction, K), spec)
 
 
 def _spec(P):

@@ -14,6 +14,7 @@ from golden_io import assert_lists_identical
 from robust_checks import check_geomed_chain as _check_chain
 from robust_checks import nan_clients as _nan_clients
 from robust_checks import same_bits as _same_bits
+from robust_fuzz_cases import round_updates
 
 pytestmark = pytest.mark.gpu
 
@@ -399,33 +400,9 @@ def _byzantine_count(fraction, K):
 
 
 def _round_updates(seed, K, spec, fraction=FRACTION):
-    """K updates of the model ``spec`` ([(shape, dtype)]): honest ones are base + sigma_k * noise with
-    graded sigma_k = 0.05 * (1 + 0.25 * rank) in shuffled order; the f = byzantine_count hostile ones
-    take honest clients' places as a sign flip, large noise and one NaN. Integer tensors hold
-    round(1000 * value). Returns (updates, hostile indices). (The generator of tests/test_gpu_krum.py.)"""
-    rng = np.random.default_rng(seed)
-    f = _byzantine_count(fraction, K)
-    sigma = 0.05 * (1 + 0.25 * rng.permutation(K))
-    hostile = sorted(int(i) for i in rng.choice(K, size=f, replace=False))
-    base = [rng.standard_normal(s) for s, _ in spec]
-    ups = []
-    for k in range(K):
-        kind = hostile.index(k) % 3 if k in hostile else None
-        u = []
-        for b, (s, dt) in zip(base, spec):
-            v = b + sigma[k] * rng.standard_normal(s)
-            if kind == 0:
-                v = -v                                           # sign flip
-            elif kind == 1:
-                v = b + 5.0 * rng.standard_normal(s)             # large noise
-            if np.dtype(dt).kind == "i":
-                v = np.round(1000.0 * v)
-            v = np.asarray(v, dtype=dt).reshape(s)
-            if kind == 2 and np.dtype(dt).kind == "f" and v.size:
-                v.reshape(-1)[v.size // 2] = np.nan              # one NaN
-            u.append(v)
-        ups.append(u)
-    return ups, hostile
+    """K updates of the model ``spec`` with f = byzantine_count(fraction, K) hostile ones: the generator the
+    robust rules' tests share (tests/robust_fuzz_cases.round_updates). Returns (updates, hostile indices)."""
+    return round_updates(seed, K, _byzantine_count(fraction, K), spec)
 
 
 def _run_round(ups, staged, parameters=None, budget=None, agg=None, uh=None):

@@ -8,6 +8,7 @@ import torch
 
 import krum_ref as kr
 from golden_io import assert_lists_identical
+from robust_fuzz_cases import krum_gaps, round_updates, selection_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -306,50 +307,21 @@ FRACTION = 0.2
 
 
 def _round_updates(seed, K, spec, fraction=FRACTION):
-    """K updates of the model ``spec`` ([(shape, dtype)]): honest ones are base + sigma_k * noise with
-    graded sigma_k = 0.05 * (1 + 0.25 * rank) in shuffled order (so the scores are separated); the
-    f = byzantine_count hostile ones take honest clients' places as a sign flip, large noise and one NaN.
-    Integer tensors hold round(1000 * value). Returns (updates, hostile indices)."""
-    rng = np.random.default_rng(seed)
-    f = kr.byzantine_count(fraction, K)
-    sigma = 0.05 * (1 + 0.25 * rng.permutation(K))
-    hostile = sorted(int(i) for i in rng.choice(K, size=f, replace=False))
-    base = [rng.standard_normal(s) for s, _ in spec]
-    ups = []
-    for k in range(K):
-        kind = hostile.index(k) % 3 if k in hostile else None
-        u = []
-        for b, (s, dt) in zip(base, spec):
-            v = b + sigma[k] * rng.standard_normal(s)
-            if kind == 0:
-                v = -v                                           # sign flip
-            elif kind == 1:
-                v = b + 5.0 * rng.standard_normal(s)             # large noise
-            if np.dtype(dt).kind == "i":
-                v = np.round(1000.0 * v)
-            v = np.asarray(v, dtype=dt).reshape(s)
-            if kind == 2 and np.dtype(dt).kind == "f" and v.size:
-                v.reshape(-1)[v.size // 2] = np.nan              # one NaN
-            u.append(v)
-        ups.append(u)
-    return ups, hostile
+    """K updates of the model ``spec`` with f = byzantine_count(fraction, K) hostile ones: the generator the
+    robust rules' tests share (tests/robust_fuzz_cases.round_updates). Returns (updates, hostile indices)."""
+    return round_updates(seed, K, kr.byzantine_count(fraction, K), spec)
 
 
 def _selection(ups, m, what):
     """The oracle's selection, after asserting the precondition in float64 on the CPU: the relative
     score gaps between the best and second-best client and between the m-th and (m+1)-th are at least
-    10 x the distance bound, so the kernel's rounding cannot change the selection."""
-    from fedn_amd import ops
+    10 x the distance bound, so the kernel's rounding cannot change the selection (the gaps and their one
+    structural exception, at K <= 3: tests/robust_fuzz_cases.krum_gaps)."""
     K = len(ups)
     f = kr.byzantine_count(FRACTION, K)
     D = kr.model_distances(ups)
-    sc = sorted(kr.scores(D.tolist(), f))
-    sizes = [np.asarray(a).size for a in ups[0]]
-    bound = 10 * max(ops.sqdist_rtol(np.asarray(a).dtype, n) for a, n in zip(ups[0], sizes))
-    gaps = []
-    for lo in sorted({0, m - 1}):
-        if lo + 1 < K and np.isfinite(sc[lo]):
-            gaps.append((sc[lo + 1] - sc[lo]) / sc[lo + 1] if np.isfinite(sc[lo + 1]) else np.inf)
+    bound = selection_bound(ups)
+    gaps = krum_gaps(D, f, m)
     print(f"{what}: score gaps {gaps}, needed {bound:.2e}")
     assert all(g >= bound for g in gaps), f"{what}: precondition — score gaps {gaps} below {bound:.2e}: pick another seed"
     return f, kr.select(D.tolist(), f, m)

@@ -227,9 +227,9 @@ def test_late_round_through_the_ring(rule, center, monkeypatch):
 def test_late_round_in_hbm(rule, center, monkeypatch):
     """Every update in HBM: one late launch per dtype group, so the results reach the pinned host buffers
     only once the spins are over — the closing synchronise of ``result`` and ``select_mean`` and the D2H
-    behind the launches are what the host's read relies on. (The two iterated rules end their last pass
-    with a synchronising read of d: their closing synchronise finds the stream drained but for the
-    centre's D2H.)"""
+    behind the launches are what the host's read relies on. (The two iterated rules launch once per slice
+    of a group here too, on the updates in place, and end their last pass with a synchronising read of d:
+    their closing synchronise finds the stream drained but for the centre's D2H.)"""
     what = f"{rule} in HBM"
     copy, compute = side_by_side_streams()
     with torch.cuda.stream(compute):
