@@ -132,6 +132,10 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
         ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # K, keep, P, stream
+    "fa_gaussian_noise": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,   # out, x (or NULL), dtype, sigma
+        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,                 # seed, stream_id, round_id
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),                 # offset, P, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -155,7 +159,7 @@ PROBE_EXPORTS = {
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

@@ -92,6 +92,7 @@ size_t dt_size(int dt) {
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
 #include "cclip.h"            // one centred-clipping step and the K squared distances to it (k_cclip_dist, fa_centered_clip_step)
+#include "dp_noise.h"         // Philox Gaussian noise added to a buffer, DP-FedAvg (k_gaussian_noise, fa_gaussian_noise)
 
 }  // namespace
 
@@ -812,6 +813,32 @@ int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* 
     return for_dtype(upd_dtype, [&](auto t) {
         return launch_cclip_dist<decltype(t)>(out, center, dist, updates, cc, K, P, accumulate, work, st);
     });
+}
+
+int fa_gaussian_noise(void* out, const void* x, int dtype, double sigma, uint64_t seed, uint32_t stream_id,
+                      uint32_t round_id, int64_t offset, int64_t P, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (P < 0 || offset < 0) return fail(FA_EINVAL, "fa_gaussian_noise: negative size or offset (P=%lld, offset=%lld)",
+                                         (long long)P, (long long)offset);
+    if (offset > INT64_MAX - P)
+        return fail(FA_EINVAL, "fa_gaussian_noise: offset + P passes 2^63 - 1 (offset=%lld, P=%lld)", (long long)offset,
+                    (long long)P);
+    if (!out && P > 0) return fail(FA_EINVAL, "fa_gaussian_noise: out is NULL");
+    if (!(sigma >= 0.0) || !std::isfinite(sigma))
+        return fail(FA_EINVAL, "fa_gaussian_noise: sigma must be finite and >= 0 (got %g)", sigma);
+    if (dtype != FA_F32 && dtype != FA_F64 && dtype != FA_F16)
+        return fail(FA_EDTYPE, "fa_gaussian_noise: dtype %d (float32, float64 or float16)", dtype);
+    if (x && x != out && P > 0) {                            // in place or disjoint, nothing between
+        const uintptr_t a = reinterpret_cast<uintptr_t>(out), b = reinterpret_cast<uintptr_t>(x);
+        const uintptr_t len = (uintptr_t)P * dt_size(dtype);
+        if (a < b + len && b < a + len)
+            return fail(FA_EINVAL, "fa_gaussian_noise: out and x overlap without being the same buffer");
+    }
+    if (P == 0) return FA_OK;
+    if (dtype == FA_F32) return launch_gaussian_noise<float>(out, x, sigma, seed, stream_id, round_id, offset, P, st);
+    if (dtype == FA_F64) return launch_gaussian_noise<double>(out, x, sigma, seed, stream_id, round_id, offset, P, st);
+    return launch_gaussian_noise<f16>(out, x, sigma, seed, stream_id, round_id, offset, P, st);
 }
 
 #ifdef FEDAGG_PROBES

@@ -478,6 +478,55 @@ def centered_clip_step(updates, center, coef, out=None, dist=None, accumulate=Fa
     return (out if store else None), dist
 
 
+NOISE_DTYPES = (torch.float32, torch.float64, torch.float16)      # order_mean_dtype's outputs
+
+
+def gaussian_noise(out, x=None, *, sigma, seed, stream_id=0, round_id=0, offset=0, stream=None):
+    """Gaussian noise added to a buffer on device (``fa_gaussian_noise``, kernel ``k_gaussian_noise``):
+    ``out[j] = O(double(x[j]) + sigma * z(offset + j))`` with ``z(i)`` the N(0, 1) deviate that is a pure
+    function of ``(seed, stream_id, round_id, i)`` (Philox4x32-10 and Box-Muller in float64, DESIGN.md
+    §3.12; ``tests/dpnoise_ref.py`` restates it in numpy). The product and the sum are rounded once in
+    float64 and the result once to ``out``'s dtype. The same bits on every call, for every split of a
+    range into calls at their offsets and at every pointer alignment.
+
+    out        flat device tensor, float32 / float64 / float16 (written)
+    x          ``out`` itself (in place, the normal use), a tensor of the same dtype, length and device
+               that does not overlap it, or None: zeros
+    sigma      the noise's standard deviation, finite and >= 0
+    seed       0 .. 2^64 - 1
+    stream_id, round_id   0 .. 2^32 - 1: the dtype group and the round of a session
+    offset     the index of ``out[0]`` in the stream, >= 0, ``offset + len(out) <= 2^63 - 1``
+    """
+    lib = _abi.load()
+    P = out.numel() if isinstance(out, torch.Tensor) else 0
+    _check_dev("out", out, P, None)
+    if out.dtype not in NOISE_DTYPES:
+        raise TypeError(f"gaussian_noise: out must be float32, float64 or float16, got {out.dtype}")
+    if x is not None:
+        _check_dev("x", x, P, out.device)
+        if x.dtype != out.dtype:
+            raise TypeError(f"gaussian_noise: x is {x.dtype}, out is {out.dtype}")
+        a, b, nbytes = out.data_ptr(), x.data_ptr(), P * out.element_size()
+        if a != b and a < b + nbytes and b < a + nbytes:
+            raise ValueError("gaussian_noise: out and x overlap without being the same buffer")
+    sigma = float(sigma)
+    if not (sigma >= 0.0 and sigma != float("inf")):
+        raise ValueError(f"gaussian_noise: sigma must be finite and >= 0, got {sigma}")
+    for name, v, bits in (("seed", seed, 64), ("stream_id", stream_id, 32), ("round_id", round_id, 32), ("offset", offset, 63)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << bits:
+            raise ValueError(f"gaussian_noise: {name} must be an int in 0 .. 2^{bits} - 1, got {v!r}")
+    if int(offset) + P > (1 << 63) - 1:
+        raise ValueError(f"gaussian_noise: offset + len(out) passes 2^63 - 1 (offset={offset}, {P} elements)")
+    if P == 0:
+        return out
+    with _on(out.device):
+        st = _stream_handle(out, stream)
+        rc = lib.fa_gaussian_noise(out.data_ptr(), x.data_ptr() if x is not None else None, fa_dtype(out), sigma,
+                                   int(seed), int(stream_id), int(round_id), int(offset), P, st)
+    _abi.check(rc)
+    return out
+
+
 def running_mean(g, m, a, b, T, stream=None):
     """``g = (g*a + m*b)/T`` in place (``fa_running_mean``): one step of the reference's
     incremental server-function example (sf_incremental_aggregation.py:36-37)."""

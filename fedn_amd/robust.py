@@ -40,6 +40,12 @@ Bulyan (El Mhamdi, Guerraoui and Rouault) joins the two kinds:
 matrix) and averages, per coordinate, the ``theta - 2f`` of their values closest to their median
 (``fa_median_window_mean``, kernel ``k_median_window``).
 
+Central DP-FedAvg (McMahan, Ramage, Talwar and Zhang) is no robust rule but shares the
+frame: ``dp_clipped_mean(center_arrays, clip, noise_multiplier, seed, round_id)`` is one step of centred
+clipping around the global model followed by Gaussian noise added to the result on the device
+(``fa_gaussian_noise``, kernel ``k_gaussian_noise``), a pure function of ``(seed, round, dtype group,
+element)``.
+
 All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
 ``ops.MAX_ORDER_K`` (64) updates per round.
 
@@ -231,6 +237,7 @@ class RobustPipeline:
         self.weights, self.distances = None, None   # geometric_median: the last pass's beta, sqrt(d)
         self.excluded, self.trace = [], []          # ... clients shut out as non-finite; (beta, d) per pass
         self.coefficients = None                    # centered_clip: the last pass's clipping coefficients
+        self.sigma, self.clipped = None, None       # dp_clipped_mean: the noise's std, clients scaled down
         self.time_pack = 0.0
         self.time_d2h = 0.0
         self.add(first, tag)
@@ -540,6 +547,62 @@ class RobustPipeline:
 
         out = self._round(body, self._pack_center(center_arrays))
         self.coefficients, d = self.trace[-1]        # the last pass's (coef, d)
+        with np.errstate(invalid="ignore"):
+            self.distances = np.sqrt(d)
+        return out
+
+    def dp_clipped_mean(self, center_arrays, clip, noise_multiplier, seed, round_id):
+        """Central DP-FedAvg with flat clipping (McMahan, Ramage, Talwar and Zhang): the
+        global model ``center_arrays`` moved by the mean of the updates' differences to it, each clipped
+        to the norm ``clip``, plus Gaussian noise of standard deviation ``sigma = (noise_multiplier * clip)
+        / K_good`` on every parameter, as host arrays like :meth:`result`'s.
+
+        The frame and the first two passes are :meth:`centered_clip`'s at one iteration: pass 0 gives the K
+        distances to the global model (a client with a non-finite one is excluded), one clipping pass moves
+        the centre in place with ``clip_coefficients(d, clip)``. Then ONE launch per dtype group adds the
+        noise to the centre in place on the compute stream (``ops.gaussian_noise``, kernel
+        ``k_gaussian_noise``) — behind the clipping pass and ahead of the centre's copy to the host — with
+        ``stream_id`` the group's index in ``layout.groups`` and ``offset`` 0: the noise is a pure function
+        of ``(seed, round_id, group, element)``, the same bits wherever the updates sit. With
+        ``noise_multiplier = 0`` nothing is launched and the result is ``centered_clip(center, 1, clip)``
+        bit for bit.
+
+        Kept on the pipeline: what :meth:`centered_clip` keeps, ``sigma`` (float64) and ``clipped``, the
+        number of clients whose difference was scaled down (``lambda < 1``)."""
+        K = self._clients()
+        if not (clip > 0 and np.isfinite(clip)) or not (noise_multiplier >= 0 and np.isfinite(noise_multiplier)):
+            raise ValueError(f"clip={clip}, noise_multiplier={noise_multiplier}")
+        for name, v, bits in (("seed", seed, 64), ("round_id", round_id, 32)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 1 << bits:
+                raise ValueError(f"{name} must be an int in 0 .. 2^{bits} - 1")
+        self.coefficients, self.distances, self.excluded, self.trace = None, None, [], []
+        self.sigma, self.clipped = None, None
+
+        def body(cen):
+            d = self._clip_pass(np.zeros(K, dtype=np.float64), cen, False)
+            good = np.isfinite(d)
+            self.excluded = [k for k in range(K) if not good[k]]
+            if not good.any():
+                raise ValueError(f"no client has a finite distance to the global model: {d}")
+            with np.errstate(invalid="ignore"):
+                self.clipped = int((np.sqrt(d[good]) > np.float64(clip)).sum())
+            d = self._clip_pass(clip_coefficients(d, clip), cen, True)
+            if not np.isfinite(d[good]).all():
+                raise ValueError(f"a distance turned non-finite after the clipping step: {d}")
+            self.sigma = (np.float64(noise_multiplier) * np.float64(clip)) / np.float64(int(good.sum()))
+            if noise_multiplier > 0:
+                for g, dt in enumerate(self.layout.groups):
+                    if self.layout.group_elems[dt] == 0:         # only empty tensors: no launch
+                        continue
+                    k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    k0.record(self.compute)
+                    ops.gaussian_noise(cen[dt], cen[dt], sigma=float(self.sigma), seed=int(seed), stream_id=g,
+                                       round_id=int(round_id), offset=0, stream=self.compute)
+                    k1.record(self.compute)
+                    self._kern.append((k0, k1))
+
+        out = self._round(body, self._pack_center(center_arrays))
+        self.coefficients, d = self.trace[-1]        # the clipping pass's (coef, d)
         with np.errstate(invalid="ignore"):
             self.distances = np.sqrt(d)
         return out

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 13
+#define FA_ABI_VERSION 14
 
 /* element type codes */
 enum fa_dtype {
@@ -505,6 +505,33 @@ int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* 
  */
 int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype,
                           int K, int keep, int64_t P, void* stream);
+
+/*
+ * fa_gaussian_noise (ABI 14): Gaussian noise for central DP-FedAvg (McMahan, Ramage, Talwar and Zhang, 2018),
+ * added to a buffer: out[j] = O(double(x[j]) + sigma * z(offset + j)), j in [0, P), with z(i) the N(0,1)
+ * deviate that is a pure function of (seed, stream_id, round_id, i) — DESIGN.md §3.12:
+ *     (x0, x1, x2, x3) = Philox4x32-10(ctr = (i mod 2^32, i >> 32, stream_id, round_id),
+ *                                      key = (seed mod 2^32, seed >> 32))
+ *     u1 = ((x0 >> 5) 2^26 + (x1 >> 6) + 1) 2^-53 in (0, 1],   u2 = ((x2 >> 5) 2^26 + (x3 >> 6)) 2^-53 in [0, 1)
+ *     z = sqrt(-2 log(u1)) cos(TWO_PI u2) in float64 (TWO_PI the float64 nearest 2 pi), |z| <= 8.58.
+ * The product sigma z and the sum are each rounded once in float64 (no FMA) and the result is converted
+ * ONCE to the output type; a float16 output is rounded straight from float64. The bits of the uniforms are
+ * the definition's; log and cos are the device library's float64 functions (DESIGN.md §3.12 has the
+ * measured distance to a correctly rounded z). One block per element: the same bits for every split of
+ * [0, P) into calls at their offsets, for every grid and every pointer alignment.
+ *
+ * out      DEVICE buffer of P elements of dtype (written: exactly out[0 .. P))
+ * x        DEVICE buffer of P elements of dtype; `out` itself (in place, the normal use), a buffer that does
+ *          not overlap it, or NULL: zeros (out float64, x NULL, sigma 1 gives z itself)
+ * dtype    F32, F64 or F16: the output types of the robust rules (bf16 is never one)
+ * sigma    the noise's standard deviation, finite and >= 0
+ * offset   the index of out[0] in the stream, >= 0, offset + P <= 2^63 - 1
+ * FA_EINVAL: a null out with P > 0, P < 0, offset < 0, offset + P past 2^63 - 1, a sigma that is negative
+ * or not finite, out overlapping x without being equal to it; FA_EDTYPE: any other dtype — all before any
+ * HIP call. P = 0 is FA_OK with no launch. fa_last_kernel reports "k_gaussian_noise".
+ */
+int fa_gaussian_noise(void* out, const void* x, int dtype, double sigma, uint64_t seed, uint32_t stream_id,
+                      uint32_t round_id, int64_t offset, int64_t P, void* stream);
 
 #ifdef __cplusplus
 }
