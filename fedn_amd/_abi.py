@@ -136,6 +136,10 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,   # out, x (or NULL), dtype, sigma
         ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,                 # seed, stream_id, round_id
         ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]),                 # offset, P, stream
+    "fa_clip_fold": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,   # out (or NULL), out_dtype, carry_out, carry_in (or NULL)
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,    # center, updates, upd_dtype
+        ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # coef, K, P, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -159,7 +163,7 @@ PROBE_EXPORTS = {
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

@@ -44,6 +44,7 @@ with a shim ``fedn/network/combiner/aggregators/centeredclip.py`` (INTEGRATION.m
 import logging
 import math
 
+from .. import ops
 from ..exceptions import InvalidParameterError
 from ..parameters import Parameters
 from . import trimmedmean
@@ -59,6 +60,9 @@ class Aggregator(trimmedmean.Aggregator):
     default_parameters = {"iterations": 3}
     parameter_schema = {"tau": float, "iterations": int}
     fraction_parameter = None
+    # The pipeline's rule takes ops.MAX_CLIP_K updates (the chunked fold); this plug-in's
+    # refusal past 64 is its documented behaviour and stays until it is lifted here, in this one line.
+    max_updates = ops.MAX_ORDER_K
 
     def __init__(self, update_handler, device=None, hbm_budget=None):
         super().__init__(update_handler, device=device, hbm_budget=hbm_budget)

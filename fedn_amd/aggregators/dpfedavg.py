@@ -34,8 +34,14 @@ denominator — and, as in the rest of the family, a client chooses its own ``nu
 The round's noise stream is ``round_id``, a per-instance counter incremented on EVERY ``combine_models``
 call (a refused or failed one too), so no two rounds of a session share one.
 
+A round takes up to ``ops.MAX_CLIP_K`` = 1024 admitted updates, not the family's 64: ``sigma`` falls as
+``1 / K_good``, so the same privacy costs the model less the larger the cohort is. Past 64 updates the
+clipped mean is a chain of ``fa_clip_fold`` launches over chunks of 64 clients that carries the accumulator
+in the compute type (kernel ``k_clip_fold``): the same definition bit for bit. More than
+1024 are logged, the round is ``(None, data)`` and nothing is deleted.
+
 The global model, the contract, the ``data`` keys, the delete-after-result rule, the excluded non-finite
-clients and the refusals are the centred-clipping plug-in's (centeredclip.py, trimmedmean.py). After a
+clients and the other refusals are the centred-clipping plug-in's (centeredclip.py, trimmedmean.py). After a
 round ``agg.sigma`` holds the noise's standard deviation, ``agg.clipped`` the number of clients whose
 update was scaled down, ``agg.distances`` every client's distance to the clipped mean and
 ``agg.excluded`` the excluded clients' FIFO indices; all are logged at info level. The seed never is.
@@ -47,6 +53,7 @@ import logging
 import math
 import secrets
 
+from .. import ops
 from ..exceptions import InvalidParameterError
 from ..parameters import Parameters
 from . import centeredclip
@@ -59,6 +66,7 @@ class Aggregator(centeredclip.Aggregator):
 
     default_parameters = {}
     parameter_schema = {"clip": float, "noise_multiplier": float, "seed": int}
+    max_updates = ops.MAX_CLIP_K          # the noise shrinks with the cohort: rounds past 64 fold by chunks
 
     def __init__(self, update_handler, device=None, hbm_budget=None):
         super().__init__(update_handler, device=device, hbm_budget=hbm_budget)

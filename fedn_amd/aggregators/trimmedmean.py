@@ -25,8 +25,8 @@ Contract (AggregatorBase's and FEDn's, fedavg.py:22-83):
 
 Limits: one device (``FEDN_AMD_DEVICES`` with several entries, parameter-sliced staged updates and
 androidhelper sessions are refused: every update is logged and skipped, the round is ``(None, data)``);
-at most 64 admitted updates per round — more are logged, the round is ``(None, data)`` and nothing is
-deleted.
+at most ``max_updates`` admitted updates per round (64 here) — more are logged, the round is
+``(None, data)`` and nothing is deleted.
 """
 import contextlib
 import logging
@@ -56,6 +56,7 @@ class Aggregator(AggregatorBase):
     parameter_schema = PARAMETER_SCHEMA
     fraction_parameter = "trim_fraction"      # the one parameter, a float in [0, fraction_bound) (subclasses rename it)
     fraction_bound = 0.5                      # ... and its exclusive upper bound (bulyan.py lowers it)
+    max_updates = ops.MAX_ORDER_K             # admitted updates a round takes at most (dpfedavg.py raises it)
 
     def __init__(self, update_handler, device=None, hbm_budget=None):
         super().__init__(update_handler)
@@ -121,7 +122,7 @@ class Aggregator(AggregatorBase):
 
         pipe = None
         admitted = []             # ModelUpdates in the pipeline, FIFO: deleted once the result exists
-        over = 0                  # updates past the 64 one launch takes
+        over = 0                  # updates past the max_updates a round takes
         logger.info("AGGREGATOR({}): Aggregating model updates... ".format(self.name))
         with contextlib.closing(queued_updates(self.update_handler, helper, size_box=self._ahead_size)) as updates:
             for model_update, load in updates:
@@ -133,7 +134,7 @@ class Aggregator(AggregatorBase):
                     tic = time.time()
                     if helper_kind(helper) == "androidhelper":
                         raise UnsupportedRound(f"the {self.name} aggregator does not serve androidhelper sessions")
-                    if len(admitted) >= ops.MAX_ORDER_K:
+                    if len(admitted) >= self.max_updates:
                         over += 1                 # counted, not staged: the round is refused below
                     elif pipe is None:
                         pipe = self._live = RobustPipeline(self.device or default_device(), model_next, tag=model_update,
@@ -153,7 +154,7 @@ class Aggregator(AggregatorBase):
             return None, data
         if over:
             logger.error(f"AGGREGATOR({self.name}): {K + over} updates admitted, a round takes at most "
-                         f"{ops.MAX_ORDER_K}; nothing aggregated, nothing deleted")
+                         f"{self.max_updates}; nothing aggregated, nothing deleted")
             return None, data
         try:
             tic = time.time()

@@ -92,6 +92,7 @@ size_t dt_size(int dt) {
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
 #include "cclip.h"            // one centred-clipping step and the K squared distances to it (k_cclip_dist, fa_centered_clip_step)
+#include "clip_fold.h"        // the clipping fold carried across chunks of more than 64 clients (k_clip_fold, fa_clip_fold)
 #include "dp_noise.h"         // Philox Gaussian noise added to a buffer, DP-FedAvg (k_gaussian_noise, fa_gaussian_noise)
 
 }  // namespace
@@ -812,6 +813,25 @@ int fa_centered_clip_step(void* out, const void* center, int out_dtype, double* 
     if (accumulate && P == 0) return FA_OK;                  // nothing to add: no launch
     return for_dtype(upd_dtype, [&](auto t) {
         return launch_cclip_dist<decltype(t)>(out, center, dist, updates, cc, K, P, accumulate, work, st);
+    });
+}
+
+int fa_clip_fold(void* out, int out_dtype, void* carry_out, const void* carry_in, const void* center,
+                 const void* const* updates, int upd_dtype, const double* coef, int K, int64_t P, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double cc[kMaxK];
+    if (const int rc = wm_check_step("fa_clip_fold", "coef", "move a centre", (out || carry_out) && center && coef && updates,
+                                     out_dtype, upd_dtype, coef, K, P, cc))
+        return rc;
+    if (P == 0) return FA_OK;                                // (an empty buffer may be a null pointer)
+    const size_t csize = pair_family(upd_dtype) == 32 ? 4 : 8;
+    if (const int rc = clip_fold_check_overlap(out, carry_out, carry_in, center, updates, K, P, dt_size(out_dtype), csize,
+                                               dt_size(upd_dtype)))
+        return rc;
+    if (const int rc = check_updates("fa_clip_fold", updates, K)) return rc;
+    return for_dtype(upd_dtype, [&](auto t) {
+        return launch_clip_fold<decltype(t)>(out, carry_out, carry_in, center, updates, cc, K, P, st);
     });
 }
 

@@ -478,6 +478,82 @@ def centered_clip_step(updates, center, coef, out=None, dist=None, accumulate=Fa
     return (out if store else None), dist
 
 
+MAX_CLIP_K = 1024     # clients of one round of the clipping rules that fold by chunks (clip_fold): 16 launches' tables
+
+
+def clip_compute_dtype(upd_dt):
+    """The compute type of the distance and clipping kernels for updates of torch dtype ``upd_dt``: float32
+    for float32 / float16 / bfloat16, float64 for float64 / int32 / int64. A carry of :func:`clip_fold` has it."""
+    if upd_dt in _SQDIST_F32:
+        return torch.float32
+    if upd_dt in _SQDIST_F64:
+        return torch.float64
+    raise TypeError(f"clip_fold: dtype {upd_dt} is not supported")
+
+
+def clip_fold(updates, center, coef, out=None, carry_in=None, carry_out=None, stream=None):
+    """Up to 64 clients of a centred-clipping step folded into a running accumulator on device
+    (``fa_clip_fold``, kernel ``k_clip_fold``): per element ``acc = carry_in`` (else the centre), then
+    ``acc = acc + coef[k] * (u_k - center)`` over the clients with a nonzero coefficient in index order, every
+    operation rounded once in the compute type; ``carry_out = acc`` and ``out = acc`` rounded once to
+    :func:`order_mean_dtype` of the updates' dtype. A chain of calls over consecutive chunks of a round — the
+    first without ``carry_in``, the last with ``out`` — is :func:`centered_clip_step`'s new point bit for bit,
+    for any number of clients and wherever the chain is cut. Returns ``(out, carry_out)``
+    as given; the same bits on every call.
+
+    updates    1 <= K <= 64 flat device tensors of one dtype (float32 / float64 / float16 / bfloat16 /
+               int32 / int64) and one length
+    center     flat device tensor of :func:`order_mean_dtype` of the updates' dtype, of the same length;
+               the differences are taken to it, and it is not modified unless ``out`` is it
+    coef       K coefficients, finite and >= 0; a client with coefficient 0 is not read; all zero is legal
+    out        None, ``center`` itself (in place) or a tensor like it that overlaps nothing else
+    carry_in   None, or the accumulator so far: a flat device tensor of :func:`clip_compute_dtype`
+    carry_out  None, ``carry_in`` itself, or a tensor like it that overlaps nothing else; at least one of
+               ``out`` and ``carry_out`` is given
+    """
+    lib = _abi.load()
+    K, P, dev, upd_dt = _distance_updates("clip_fold", updates)
+    out_dt, c_dt = order_mean_dtype(upd_dt), clip_compute_dtype(upd_dt)
+    _check_point("clip_fold", "center", center, P, dev, upd_dt)
+    coef = [float(c) for c in coef]
+    if len(coef) != K:
+        raise ValueError(f"clip_fold: {len(coef)} coefficients for {K} updates")
+    if out is None and carry_out is None:
+        raise ValueError("clip_fold: one of out and carry_out is needed")
+    if out is not None:
+        _check_point("clip_fold", "out", out, P, dev, upd_dt)
+    for arg, t in (("carry_in", carry_in), ("carry_out", carry_out)):
+        if t is not None:
+            _check_dev(arg, t, P, dev)
+            if t.dtype != c_dt:
+                raise TypeError(f"clip_fold: {arg} must be {c_dt} for {upd_dt} updates, got {t.dtype}")
+    # the two legal aliases: out is the centre, carry_out is carry_in; any other overlap that involves one of
+    # those four buffers is refused (the library checks the same at the pointers' level)
+    named = [("out", out), ("carry_out", carry_out), ("carry_in", carry_in), ("center", center)]
+    spans = [(n, t.data_ptr(), P * t.element_size()) for n, t in named if t is not None]
+    for i, (na, a, la) in enumerate(spans):
+        for nb, b, lb in spans[i + 1:]:
+            if a == b and (na, nb) in (("out", "center"), ("carry_out", "carry_in")):
+                continue
+            if a < b + lb and b < a + la:
+                raise ValueError(f"clip_fold: {na} and {nb} overlap")
+        for k, u in enumerate(updates):
+            b, lb = u.data_ptr(), P * u.element_size()
+            if a < b + lb and b < a + la:
+                raise ValueError(f"clip_fold: {na} and updates[{k}] overlap")
+    if P == 0:
+        return out, carry_out
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = lib.fa_clip_fold(out.data_ptr() if out is not None else None, fa_dtype(out_dt),
+                              carry_out.data_ptr() if carry_out is not None else None,
+                              carry_in.data_ptr() if carry_in is not None else None, center.data_ptr(),
+                              _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt),
+                              _abi.double_array(coef), K, P, ctypes_stream(s))
+    _abi.check(rc)
+    return out, carry_out
+
+
 NOISE_DTYPES = (torch.float32, torch.float64, torch.float16)      # order_mean_dtype's outputs
 
 

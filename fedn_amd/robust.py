@@ -46,8 +46,11 @@ clipping around the global model followed by Gaussian noise added to the result 
 (``fa_gaussian_noise``, kernel ``k_gaussian_noise``), a pure function of ``(seed, round, dtype group,
 element)``.
 
-All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only, at most
-``ops.MAX_ORDER_K`` (64) updates per round.
+All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only. A round takes at most
+``ops.MAX_ORDER_K`` (64) updates — one launch's table, one sorting network, one K x K matrix — except the
+two clipping rules, ``centered_clip`` and ``dp_clipped_mean``, which take ``ops.MAX_CLIP_K`` (1024): past 64
+their step is a chain of ``fa_clip_fold`` launches over chunks of 64 clients that carries the accumulator in
+the compute type (kernel ``k_clip_fold``), the same definition bit for bit.
 
 Stream ordering (the rules DESIGN.md records for fresh HBM, §3.7): a buffer is allocated on the
 stream that first writes it (staged updates and the ring on the copy stream, results on the compute
@@ -283,12 +286,13 @@ class RobustPipeline:
         return arrays
 
     # ---- reduction -------------------------------------------------------------------
-    def _clients(self):
-        """K, the round's size, within what one launch's table holds: every rule's first check, ahead of
-        those of its own arguments."""
+    def _clients(self, cap=ops.MAX_ORDER_K):
+        """K, the round's size, within the rule's ``cap`` — what one launch's table holds, or
+        ``ops.MAX_CLIP_K`` for the two clipping rules, which fold by chunks: every rule's first check, ahead
+        of those of its own arguments."""
         K = len(self.updates)
-        if not 1 <= K <= ops.MAX_ORDER_K:
-            raise ValueError(f"a robust round takes 1..{ops.MAX_ORDER_K} updates, got {K}")
+        if not 1 <= K <= cap:
+            raise ValueError(f"a robust round takes 1..{cap} updates, got {K}")
         return K
 
     def _round(self, body, center=None):
@@ -526,9 +530,12 @@ class RobustPipeline:
         non-finite global model also causes — or when a later distance of a remaining client turns
         non-finite.
 
+        A round of more than 64 updates (up to ``ops.MAX_CLIP_K``) takes every pass by chunks of 64 clients
+        (:meth:`_clip_pass_chunked`): the same definition and the same kept values.
+
         Kept on the pipeline: ``coefficients`` (the last pass's), ``distances`` (sqrt of the last pass's
         d), ``excluded`` (FIFO indices) and ``trace`` (one ``(coef, d)`` pair per pass, float64)."""
-        K = self._clients()
+        K = self._clients(ops.MAX_CLIP_K)
         if iterations < 0 or not (tau > 0 and np.isfinite(tau)):
             raise ValueError(f"iterations={iterations}, tau={tau}")
         L = int(iterations)
@@ -569,7 +576,7 @@ class RobustPipeline:
 
         Kept on the pipeline: what :meth:`centered_clip` keeps, ``sigma`` (float64) and ``clipped``, the
         number of clients whose difference was scaled down (``lambda < 1``)."""
-        K = self._clients()
+        K = self._clients(ops.MAX_CLIP_K)
         if not (clip > 0 and np.isfinite(clip)) or not (noise_multiplier >= 0 and np.isfinite(noise_multiplier)):
             raise ValueError(f"clip={clip}, noise_multiplier={noise_multiplier}")
         for name, v, bits in (("seed", seed, 64), ("round_id", round_id, 32)):
@@ -635,6 +642,8 @@ class RobustPipeline:
         the new point as a float64 host array; with ``store`` the centre ``cen`` (device tensors by dtype
         group) is moved in place. Appends ``(coef, d)`` to ``trace``."""
         coef = np.array(coef, dtype=np.float64)
+        if len(self.updates) > ops.MAX_ORDER_K:
+            return self._clip_pass_chunked(coef, cen, store)
 
         def group(dt):
             def step(b, lo, hi, views, stride, dist, accumulate):
@@ -645,6 +654,112 @@ class RobustPipeline:
             return step, None
 
         return self._distance_pass(len(self.updates), group, coef)
+
+    def _clip_pass_chunked(self, coef, cen, store):
+        """:meth:`_clip_pass` for a round of more than ``ops.MAX_ORDER_K`` updates: the same
+        definition, the same ``trace`` entry. Every dtype group is walked at the slice bounds, wherever the
+        updates sit, and within a slice the clients in chunks of 64 in FIFO order:
+
+          * ``store``: one ``ops.clip_fold`` per chunk that has a nonzero coefficient, over its clients with a
+            nonzero coefficient alone (the others are not read, and not uploaded). The first launch starts
+            from the centre's slice, the last writes it in place, the ones between hand the accumulator on
+            through a carry of one slice in the compute type — allocated on the compute stream, reused by
+            every slice in stream order;
+          * then, per chunk, ``ops.centered_clip_step`` with zero coefficients and nothing stored adds the
+            chunk's squared distances to the slice of the (moved) centre into its range of ``d``: that range
+            is written by the chunk's first launch of the pass and added to by the rest, in this one order —
+            the same bits whether the budget left updates on the host or not.
+
+        Host-side updates go through a ring of two buffers of at most 64 rows of one slice, one buffer per
+        launch: in a moving pass such an update is uploaded once for the fold and once for the distances,
+        the cost of ``v'`` depending on all K clients."""
+        K = len(self.updates)
+        CH = ops.MAX_ORDER_K
+        chunks = [(c0, min(K, c0 + CH)) for c0 in range(0, K, CH)]
+        live = [[k for k in range(c0, c1) if coef[k] != 0.0] for c0, c1 in chunks] if store else []
+        folds = [ks for ks in live if ks]
+        d = torch.zeros(K, dtype=torch.float64, device=self.device)
+        written = [False] * len(chunks)
+        zeros = [0.0] * CH
+        for dt in self.layout.groups:
+            n = self.layout.group_elems[dt]
+            if n == 0:                               # only empty tensors: no launch
+                continue
+            tdt = ops.torch_dtype(dt)
+            isz, goff = dt.itemsize, self.layout.group_byte_offset[dt]
+            step = min(n, max(SLICE_ALIGN, SLICE_BYTES // isz // SLICE_ALIGN * SLICE_ALIGN))
+            host = [k for k in range(K) if not isinstance(self.updates[k], StagedModel)]
+            flats = {k: self._host_flat(self.updates[k], dt) for k in host}
+            rows = max((sum(1 for k in range(c0, c1) if k in flats) for c0, c1 in chunks), default=0)
+            ring, consumed, turn = None, [None, None], 0
+            if rows:
+                with torch.cuda.stream(self.copy):   # allocated on the stream that writes it
+                    row = -(-step // SLICE_ALIGN) * SLICE_ALIGN
+                    ring = reuse.watch(torch.empty((2, rows, row), dtype=tdt, device=self.device), self.copy)
+            carry = None
+            if len(folds) > 1:                       # (on the compute stream: the current one inside _round)
+                carry = torch.empty(step, dtype=ops.clip_compute_dtype(tdt), device=self.device)
+
+            def launch(ks, lo, hi, op):
+                """``op(views)`` on slice [lo, hi) of the clients ``ks`` (one chunk's): the host-side ones
+                through the ring's next buffer."""
+                nonlocal turn
+                up = [k for k in ks if k in flats]
+                b = turn % 2
+                if up:
+                    turn += 1
+                    if consumed[b] is not None:
+                        self.copy.wait_event(consumed[b])      # the launch that read this buffer ran
+                    h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    with torch.cuda.stream(self.copy):
+                        h0.record(self.copy)
+                        for r, k in enumerate(up):
+                            for flat, off in flats[k]:         # members overlapping [lo, hi)
+                                s0, s1 = max(lo, off), min(hi, off + flat.size)
+                                if s0 < s1:
+                                    ring[b, r, s0 - lo:s1 - lo].copy_(torch.from_numpy(flat[s0 - off:s1 - off]),
+                                                                      non_blocking=True)
+                        h1.record(self.copy)
+                    self._h2d.append((h0, h1))
+                    self.compute.wait_event(h1)
+                views, r = [], 0
+                for k in ks:
+                    u = self.updates[k]
+                    if isinstance(u, StagedModel):
+                        views.append(u.dev[goff + lo * isz:goff + hi * isz].view(tdt))
+                    else:
+                        views.append(ring[b, r, :hi - lo])
+                        r += 1
+                k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                k0.record(self.compute)
+                op(views)
+                k1.record(self.compute)
+                self._kern.append((k0, k1))
+                if up:
+                    consumed[b] = torch.cuda.Event()
+                    consumed[b].record(self.compute)
+
+            for lo in range(0, n, step):
+                hi = min(n, lo + step)
+                v = cen[dt][lo:hi]
+                for i, ks in enumerate(folds):
+                    first, last = i == 0, i == len(folds) - 1
+                    acc = carry[:hi - lo] if carry is not None else None
+                    launch(ks, lo, hi, lambda views, ks=ks, first=first, last=last, acc=acc: ops.clip_fold(
+                        views, v, coef[ks], out=v if last else None, carry_in=None if first else acc,
+                        carry_out=None if last else acc, stream=self.compute))
+                for j, (c0, c1) in enumerate(chunks):
+                    launch(list(range(c0, c1)), lo, hi, lambda views, j=j, c0=c0, c1=c1: ops.centered_clip_step(
+                        views, v, zeros[:c1 - c0], dist=d[c0:c1], accumulate=written[j], store=False,
+                        stream=self.compute))
+                    written[j] = True
+            if ring is not None:
+                ring.record_stream(self.compute)
+        tic = time.perf_counter()
+        sums = d.cpu().numpy()                       # (synchronises the compute stream)
+        self.time_d2h += time.perf_counter() - tic
+        self.trace.append((coef, sums))
+        return sums
 
     def _host_flat(self, arrays, dt):
         """(flat array, element offset in the group) of the non-empty members of group ``dt``."""

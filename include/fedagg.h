@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 14
+#define FA_ABI_VERSION 15
 
 /* element type codes */
 enum fa_dtype {
@@ -532,6 +532,39 @@ int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, 
  */
 int fa_gaussian_noise(void* out, const void* x, int dtype, double sigma, uint64_t seed, uint32_t stream_id,
                       uint32_t round_id, int64_t offset, int64_t P, void* stream);
+
+/*
+ * fa_clip_fold (ABI 15): the centred-clipping fold of fa_centered_clip_step for rounds of MORE than 64
+ * clients — up to 64 clients of a round folded into a running accumulator that is carried between launches
+ * in the compute type. With C, O and c_k = C(coef[k]) as for fa_centered_clip_step, per element
+ *     acc = carry_in[p] where carry_in is given, else C(center[p]),
+ *     then over the call's clients with c_k != 0 in index order:   acc = acc + c_k (C(u_k) - C(center[p])),
+ *     carry_out[p] = acc (in C, exact),   out[p] = acc rounded once to O,   whichever is given,
+ * the difference, the product and the add each rounded once in C (no FMA, no reassociation). A client with
+ * c_k = 0 is never read. The differences are always taken to `center`, which the call does not modify
+ * unless out == center. A chain of calls over consecutive chunks of a round's clients in index order — the
+ * first without carry_in, the last with out, the ones between with both carries — gives
+ * fa_centered_clip_step's v' bit for bit, wherever the chain is cut. No distances: the
+ * caller takes them with fa_centered_clip_step at coef = 0 against the new point.
+ *
+ * out        DEVICE buffer of P elements of out_dtype, or NULL; `center` itself is legal (in place: a lane
+ *            reads its elements of the centre before it stores them)
+ * out_dtype  F32 for F32 / BF16 updates, F16 for F16, F64 for F64 / I32 / I64 (named also when out is NULL)
+ * carry_out  DEVICE buffer of P elements of C (float for F32 / F16 / BF16 updates, else double), or NULL; at
+ *            least one of out and carry_out is given
+ * carry_in   DEVICE buffer of P elements of C, or NULL; `carry_out` itself is legal
+ * center     DEVICE buffer of P elements of out_dtype
+ * updates    HOST array of K DEVICE pointers, each P elements of upd_dtype; 1 <= K <= 64
+ * coef       HOST array of K doubles, each finite and >= 0 (in C too); all zero is legal (acc passes through)
+ * FA_EINVAL: a null center, coef or updates, out and carry_out both null, a null entry of updates when
+ * P > 0, K outside 1..64, P < 0, a coef that is negative or not finite (also as a C value), and at P > 0 any
+ * overlap among out, the carries and the centre other than the two aliases above, or of one of those four
+ * with an update; FA_EDTYPE: a dtype outside the six or an out_dtype that is not the table's — all before
+ * any HIP call. P = 0 is FA_OK with no launch. The same bits on every call, for every grid and at every
+ * pointer alignment. fa_last_kernel reports "k_clip_fold".
+ */
+int fa_clip_fold(void* out, int out_dtype, void* carry_out, const void* carry_in, const void* center,
+                 const void* const* updates, int upd_dtype, const double* coef, int K, int64_t P, void* stream);
 
 #ifdef __cplusplus
 }
