@@ -30,7 +30,7 @@ FA_PG_FIRST, FA_PG_FINAL = 1, 2
  FA_TUNE_BLOCK, FA_TUNE_SUM_NOSTORE, FA_TUNE_NT_STORE, FA_TUNE_FASTDIV64, FA_TUNE_NARROW, FA_TUNE_AUTO_GEOM,
  FA_TUNE_OPT_MIX, FA_TUNE_OPT_WIN_PERIOD, FA_TUNE_OPT_WIN_W, FA_TUNE_OPT_WIN_MODE,
  FA_TUNE_AVG_WIN_PERIOD, FA_TUNE_AVG_WIN_W, FA_TUNE_AVG_WIN_MODE, FA_TUNE_OPT_WIN_PROD,
- FA_TUNE_AVG_PARK_DEPTH, FA_TUNE_AVG_PARK_SLOTS) = range(23)
+ FA_TUNE_AVG_PARK_DEPTH, FA_TUNE_AVG_PARK_SLOTS, FA_TUNE_AVG_PARK_HEIGHT, FA_TUNE_AVG_PARK_LOADPOL) = range(25)
 
 EXPORTS = {
     # name: (restype, argtypes)

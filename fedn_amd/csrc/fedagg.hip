@@ -30,6 +30,7 @@
 #include <atomic>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/fedagg.h"
@@ -79,6 +80,7 @@ size_t dt_size(int dt) {
 
 // The kernel families and their launch policy, one header each, in dependency order
 #include "fold_rules.h"      // element types, numpy's arithmetic per dtype, 16-B strips, the client table
+#include "park_partition.h"   // the parked fold's split of a model into ring tiles and tail tiles (kernel, launcher, CPU test)
 #include "fedavg_kernels.h"   // k_fedavg, k_fedavg_pipe, k_fedavg_pipe_win (the parked fold included)
 #include "fedopt_kernels.h"   // k_fedopt, k_fedopt_c, k_fedopt_cw
 #include "helper_kernels.h"   // numpyhelper primitives, the 1-norm, k_cast

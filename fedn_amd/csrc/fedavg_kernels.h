@@ -268,86 +268,117 @@ k_fedavg_pipe(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const 
     fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP>(agg, tab, K, P);
 }
 
-// The ring depth and the parked tiles per workgroup the product ships (avg_store_window has the
-// measurements).
-constexpr int kAvgParkDepth = 2, kAvgParkSlots = 2;
+// The ring depth, the parked tiles per workgroup, the tile height and the ring's load policy (1: nt)
+// the product ships (avg_store_window has the measurements).
+constexpr int kAvgParkDepth = 2, kAvgParkSlots = 2, kAvgParkHeight = 2, kAvgParkLoadPol = 1;
+
+// The cache-policy operand (aux) of the ring's buffer loads for load policy POL (fa_tune
+// AVG_PARK_LOADPOL): 0 default, 1 nt, 2 sc1, 3 sc1 nt. The bits are the compiler's gfx940-family
+// encoding of a buffer instruction's policy (bit 1: slc, printed nt; bit 4: scc, printed sc1; bit 0,
+// glc, printed sc0, stays clear) — read off the disassembly of the four instantiations, DESIGN §3.2.
+constexpr int park_load_aux(int pol) { return ((pol & 1) ? 2 : 0) | ((pol & 2) ? 16 : 0); }
+
+constexpr int park_lcm(int a, int b) {
+    int m = a;
+    while (m % b) m += a;
+    return m;
+}
+template <int... Is, class F>
+__device__ __forceinline__ void park_static_for(std::integer_sequence<int, Is...>, F&& f) {
+    (f(std::integral_constant<int, Is>{}), ...);
+}
 
 // Store-window mode 3, "parked" (a first launch, INIT): no workgroup idles for the
 // window. The grid is the resident workgroups, each sweeping tiles blockIdx.x + i * gridDim.x. A
 // finished tile's results are parked in LDS (each lane its own 16-B pieces, piece s of lane l at
-// [s * BLK + l] of a slot) and the workgroup goes straight on to its next tile. Two compile-time
-// parameters (fa_tune AVG_PARK_DEPTH / _SLOTS): DEPTH client buffers in the load ring, SLOTS parked
-// tiles per workgroup.
-// The sweep is one stream of (tile, client) positions; buffer i holds stream position i mod DEPTH,
-// and the step that consumes a position first issues the loads of the position DEPTH - 1 ahead into
-// the buffer the step before it consumed. The load cursor (lt, lk) runs ahead of the consume cursor
-// (t, k) across tile boundaries, over several tiles where K < DEPTH. What keeps the loads in flight:
-//  - the loop is counted (the workgroup's positions are known up front) and unrolled DEPTH times, so
-//    buffer indices are static and the loop has one exit; the remainder of the stream and the last
-//    DEPTH - 1 steps, which load nothing, are copies of their own behind it. (With an exit in every
-//    step, the compiler's common exit block is also a path back to the loop's head on which a step's
-//    buffer is the newest load, and every wait is sized for that.)
+// [s * BLK + l] of a slot's small tile) and the workgroup goes straight on to its next tile. Four
+// compile-time parameters (fa_tune AVG_PARK_DEPTH / _SLOTS / _HEIGHT / _LOADPOL): DEPTH client
+// buffers in the load ring, SLOTS parked tiles per workgroup, HEIGHT consecutive 16 KiB tiles of the
+// model in one "tall" tile, and the cache policy POL of the ring's loads (park_load_aux).
+// The sweep is one stream of (tall tile, client, piece) positions, the piece advancing first, then
+// the client, then the tile: a workgroup reads HEIGHT * 16 KiB of one client in a row, and the
+// positions a wave has in flight are mostly neighbours in one client's buffer. A position is 16 KiB
+// of one client whatever HEIGHT is. Buffer i holds stream position i mod DEPTH, the running values
+// x[p] belong to piece p = i mod HEIGHT, and the step that consumes a position first issues the
+// loads of the position DEPTH - 1 ahead into the buffer the step before it consumed. The load cursor
+// (lt, lk) runs ahead of the consume cursor (t, k) across tile boundaries, over several tiles where
+// K * HEIGHT < DEPTH. What keeps the loads in flight:
+//  - the loop is counted (the workgroup's positions are known up front) and unrolled lcm(DEPTH,
+//    HEIGHT) times, so buffer and piece indices are static and the loop has one exit; the remainder
+//    of the stream and the last DEPTH - 1 steps, which load nothing, are copies of their own behind
+//    it. (With an exit in every step, the compiler's common exit block is also a path back to the
+//    loop's head on which a step's buffer is the newest load, and every wait is sized for that.)
 //  - a strip is one buffer load: the position's base in a scalar descriptor, the strip in the scalar
 //    offset, the lane's offset in a loop-invariant register. (Address registers are taken from the
 //    buffer about to be loaded, and computing them waits for all but one load in flight.)
-// Parked tiles are stored oldest first: all of them when a poll of the clock, once per client pair,
-// finds the window open, the oldest behind the bounded wait when a tile is finished with no slot
-// free, the rest at the end of the sweep. Each wave keeps the FIFO for itself: `oldest` (a tile
-// number, -1 = none; the others follow gridDim.x apart), its slot `head`, and `count`. A lane reads
-// back only what it wrote, so there is still no barrier. Arithmetic, element order per lane, store
-// addresses and store flavour are mode 0's. The ragged tile, the last of its workgroup, goes through
-// k_fedavg_tail, all its lanes (the same arithmetic per element).
-template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS>
+// A tall tile is parked piece by piece while its last client is consumed, and counts as parked with
+// its last piece. Parked tiles are stored oldest first: all of them when a poll of the clock, once
+// per client pair, finds the window open, the oldest behind the bounded wait when a tile is about to
+// be parked with no slot free, the rest at the end of the sweep. Each wave keeps the FIFO for itself:
+// `oldest` (a tall-tile number, -1 = none; the others follow gridDim.x apart), its slot `head`, and
+// `count`. A lane reads back only what it wrote, so there is still no barrier. Arithmetic, element
+// order per lane, store addresses and store flavour are mode 0's. What is no whole tall tile — up to
+// HEIGHT - 1 whole 16 KiB tiles and the ragged one — goes through k_fedavg_tail, all the lanes of
+// the workgroup park_partition.h names (the same arithmetic per element).
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS, int HEIGHT = 1, int POL = 0>
 __device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const ClientTable<typename CP::S>& tab, const int K,
                                                  const int64_t P, const uint32_t period, const uint32_t win_w) {
     using V = typename CP::V;
     static_assert(E * sizeof(X) == 16 && E * sizeof(Y) == 16, "one 16-B piece per strip");
     static_assert(DEPTH >= 2 && DEPTH <= 4, "a ring of 2, 3 or 4 client buffers");
-    static_assert((SLOTS == 1 || SLOTS == 2 || SLOTS == 4) && SLOTS * S * BLK * 16 <= 65536, "1, 2 or 4 slots of static LDS");
-    __shared__ u32x4 park[SLOTS][S * BLK];
+    static_assert(HEIGHT == 1 || HEIGHT == 2 || HEIGHT == 4, "tall tiles of 1, 2 or 4 tiles");
+    static_assert((SLOTS == 1 || SLOTS == 2 || SLOTS == 4) && SLOTS * HEIGHT * S * BLK * 16 <= 65536,
+                  "1, 2 or 4 slots of static LDS");
+    static_assert(POL >= 0 && POL <= 3, "load policy 0 (default), 1 (nt), 2 (sc1) or 3 (sc1 nt)");
+    __shared__ u32x4 park[SLOTS][HEIGHT][S * BLK];
     constexpr int64_t kTile = (int64_t)BLK * S * E;
-    const int64_t ntiles = (P + kTile - 1) / kTile, nfull = P / kTile;   // at most one ragged tile follows the whole ones
-    // this workgroup's whole tiles and stream positions
-    const int64_t mine = (int64_t)blockIdx.x < nfull ? (nfull - blockIdx.x + gridDim.x - 1) / gridDim.x : 0, npos = mine * K;
-    V x[S][E];
+    constexpr int U = park_lcm(DEPTH, HEIGHT);                           // the loop's unroll: buffer and piece both static
+    const ParkPartition part = park_partition(P, kTile, HEIGHT);
+    // this workgroup's whole tall tiles and stream positions
+    const int64_t mine = park_ring_tiles(part, gridDim.x, blockIdx.x), npos = mine * K * HEIGHT;
+    V x[HEIGHT][S][E];
     Y buf[DEPTH][S][E];
     int64_t t = blockIdx.x, lt = t, oldest = -1;                         // the tile in hand, the last one loaded from, the FIFO
     int k = 0, lk = 0, head = 0, count = 0;
     const uint32_t lane_y = threadIdx.x * (uint32_t)(E * sizeof(Y)), lane_x = threadIdx.x * (uint32_t)(E * sizeof(X));
-    auto load = [&](int64_t tt, int kk, Y (&y)[S][E]) {                  // tt < nfull: a whole tile, inside the client's buffer
-        char* base = const_cast<char*>(static_cast<const char*>(tab.ptr[kk])) + tt * (kTile * (int64_t)sizeof(Y));
+    // piece `piece` of client kk in tall tile tt < ntall: a whole 16 KiB tile, inside the client's buffer
+    auto load = [&](int64_t tt, int kk, int piece, Y (&y)[S][E]) {
+        char* base = const_cast<char*>(static_cast<const char*>(tab.ptr[kk])) + (tt * HEIGHT + piece) * (kTile * (int64_t)sizeof(Y));
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(kTile * sizeof(Y)), 0x00020000);
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_y, s * BLK * E * (int)sizeof(Y), 0);
+            const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_y, s * BLK * E * (int)sizeof(Y), park_load_aux(POL));
             __builtin_memcpy(y[s], &w, 16);
         }
     };
-    auto next = [&](int64_t& tt, int& kk) {                              // the stream position after (tt, kk)
+    auto next = [&](int64_t& tt, int& kk) {                              // the client after (tt, kk)
         if (++kk == K) {
             kk = 0;
             tt += gridDim.x;
         }
     };
     auto flush = [&]() {                                                 // the oldest parked tile
-        char* base = reinterpret_cast<char*>(agg) + oldest * (kTile * (int64_t)sizeof(X));
+        char* base = reinterpret_cast<char*>(agg) + oldest * (HEIGHT * kTile * (int64_t)sizeof(X));
 #pragma unroll
-        for (int s = 0; s < S; ++s) {
-            X xo[E];
-            const u32x4 w = park[head][s * BLK + threadIdx.x];
-            __builtin_memcpy(xo, &w, 16);
-            strip_store<X, E, NTS>(reinterpret_cast<X*>(base + (int64_t)s * BLK * E * sizeof(X) + lane_x), xo);
-        }
+        for (int p = 0; p < HEIGHT; ++p)
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                X xo[E];
+                const u32x4 w = park[head][p][s * BLK + threadIdx.x];
+                __builtin_memcpy(xo, &w, 16);
+                strip_store<X, E, NTS>(reinterpret_cast<X*>(base + (int64_t)(p * S + s) * BLK * E * sizeof(X) + lane_x), xo);
+            }
         head = (head + 1) % SLOTS;
         oldest = --count ? oldest + gridDim.x : -1;
     };
-    // one client step: `cur` holds client k of tile t
-    auto consume = [&](const Y (&cur)[S][E]) {
+    // one step of the consume cursor: `cur` holds piece PC of client k of tall tile t
+    auto consume = [&](auto pc, const Y (&cur)[S][E]) {
+        constexpr int PC = decltype(pc)::value;
         if (k == 0) {                                                    // x := updates[0] (strip_start's INIT)
 #pragma unroll
             for (int s = 0; s < S; ++s)
 #pragma unroll
-                for (int e = 0; e < E; ++e) x[s][e] = widen<Y, V>(cur[s][e]);
+                for (int e = 0; e < E; ++e) x[PC][s][e] = widen<Y, V>(cur[s][e]);
         } else {
             const typename CP::S n = tab.n[k], N = tab.N[k];
             const double r = tab.r[k];
@@ -356,101 +387,99 @@ __device__ __forceinline__ void fedavg_park_body(X* __restrict__ agg, const Clie
                 V yv[E];
 #pragma unroll
                 for (int e = 0; e < E; ++e) yv[e] = widen<Y, V>(cur[s][e]);
-                fold_strip<CP, E>(x[s], yv, n, N, r);
+                fold_strip<CP, E>(x[PC][s], yv, n, N, r);
             }
         }
-        if (k == K - 1) {                                                // the tile is finished: park it
-            if (count == SLOTS) {                                        // no slot free
-                wait_write_window(period, win_w);
-                flush();
+        if (k == K - 1) {                                                // the piece is finished: park it
+            if constexpr (PC == 0) {
+                if (count == SLOTS) {                                    // no slot free
+                    wait_write_window(period, win_w);
+                    flush();
+                }
             }
             const int slot = (head + count) % SLOTS;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 X xo[E];
 #pragma unroll
-                for (int e = 0; e < E; ++e) xo[e] = narrow<X, V>(x[s][e]);
+                for (int e = 0; e < E; ++e) xo[e] = narrow<X, V>(x[PC][s][e]);
                 u32x4 w;
                 __builtin_memcpy(&w, xo, 16);
-                park[slot][s * BLK + threadIdx.x] = w;
+                park[slot][PC][s * BLK + threadIdx.x] = w;
             }
-            if (count++ == 0) oldest = t;
-        } else if ((k & 1) && count > 0 && in_write_window(period, win_w)) {
+            if constexpr (PC == HEIGHT - 1) {
+                if (count++ == 0) oldest = t;
+            }
+        } else if (PC == HEIGHT - 1 && (k & 1) && count > 0 && in_write_window(period, win_w)) {
             do flush();
             while (count > 0);
         }
-        next(t, k);
+        if constexpr (PC == HEIGHT - 1) next(t, k);
     };
-    // a step of the full ring: the load DEPTH - 1 positions ahead is issued before buf[I] is consumed
-    auto step = [&](auto ix) {
-        constexpr int I = decltype(ix)::value;
-        next(lt, lk);
-        load(lt, lk, buf[(I + DEPTH - 1) % DEPTH]);
-        consume(buf[I]);
+    // the load cursor moves on to a position whose piece is LP, and loads it into buf[B]
+    auto fetch = [&](auto lp, auto b) {
+        constexpr int LP = decltype(lp)::value;
+        if constexpr (LP == 0) next(lt, lk);
+        load(lt, lk, LP, buf[decltype(b)::value]);
     };
-    // the last DEPTH - 1 positions, all loaded, from buf[I] on
-    auto drain = [&](auto ix) {
-        constexpr int I = decltype(ix)::value;
-#pragma unroll
-        for (int j = 0; j < DEPTH - 1; ++j) consume(buf[(I + j) % DEPTH]);
+    // step J of the unrolled ring: the load DEPTH - 1 positions ahead is issued before position J is consumed
+    auto step = [&](auto jx) {
+        constexpr int J = decltype(jx)::value;
+        fetch(std::integral_constant<int, (J + DEPTH - 1) % HEIGHT>{}, std::integral_constant<int, (J + DEPTH - 1) % DEPTH>{});
+        consume(std::integral_constant<int, J % HEIGHT>{}, buf[J % DEPTH]);
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2 % DEPTH>;
-    using I3 = std::integral_constant<int, 3 % DEPTH>;
-    if (npos >= DEPTH - 1) {
-        load(t, 0, buf[0]);                                              // DEPTH - 1 positions before the first consume
-#pragma unroll
-        for (int j = 1; j < DEPTH - 1; ++j) {
-            next(lt, lk);
-            load(lt, lk, buf[j]);
-        }
-        const int64_t nstep = npos - (DEPTH - 1);                        // steps that load
-        for (int64_t i = nstep / DEPTH; i > 0; --i) {
-            step(I0{});
-            step(I1{});
-            if constexpr (DEPTH > 2) step(I2{});
-            if constexpr (DEPTH > 3) step(I3{});
-        }
-        const int rem = (int)(nstep % DEPTH);
-        if (rem == 0) {
-            drain(I0{});
+    // the last DEPTH - 1 positions, all loaded, from position J on
+    auto drain = [&](auto jx) {
+        constexpr int J = decltype(jx)::value;
+        park_static_for(std::make_integer_sequence<int, DEPTH - 1>{}, [&](auto d) {
+            constexpr int Q = J + decltype(d)::value;
+            consume(std::integral_constant<int, Q % HEIGHT>{}, buf[Q % DEPTH]);
+        });
+    };
+    // the remainder behind the loop: `rem` < U more steps, then the drain
+    auto finish = [&](auto self, auto jx, int rem) -> void {
+        constexpr int J = decltype(jx)::value;
+        if constexpr (J == U - 1) {
+            drain(jx);
         } else {
-            step(I0{});
-            if (DEPTH == 2 || rem == 1) {
-                drain(I1{});
+            if (rem == J) {
+                drain(jx);
             } else {
-                step(I1{});
-                if (DEPTH == 3 || rem == 2) {
-                    drain(I2{});
-                } else {
-                    step(I2{});
-                    drain(I3{});
-                }
+                step(jx);
+                self(self, std::integral_constant<int, J + 1>{}, rem);
             }
         }
+    };
+    using I0 = std::integral_constant<int, 0>;
+    if (npos >= DEPTH - 1) {
+        load(t, 0, 0, buf[0]);                                           // DEPTH - 1 positions before the first consume
+        park_static_for(std::make_integer_sequence<int, DEPTH - 2>{}, [&](auto d) {
+            constexpr int Q = decltype(d)::value + 1;
+            fetch(std::integral_constant<int, Q % HEIGHT>{}, std::integral_constant<int, Q>{});
+        });
+        const int64_t nstep = npos - (DEPTH - 1);                        // steps that load
+        for (int64_t i = nstep / U; i > 0; --i) park_static_for(std::make_integer_sequence<int, U>{}, step);
+        finish(finish, I0{}, (int)(nstep % U));
     } else if (npos > 0) {                                               // a stream shorter than the ring: 1 or 2 positions
-        load(t, 0, buf[0]);
-        if (npos > 1) {
-            next(lt, lk);
-            load(lt, lk, buf[1]);
-        }
-        consume(buf[0]);
-        if (npos > 1) consume(buf[1]);
+        load(t, 0, 0, buf[0]);
+        if (npos > 1) fetch(std::integral_constant<int, 1 % HEIGHT>{}, std::integral_constant<int, 1>{});
+        consume(I0{}, buf[0]);
+        if (npos > 1) consume(std::integral_constant<int, 1 % HEIGHT>{}, buf[1]);
     }
     while (count > 0) flush();
-    if (nfull < ntiles && nfull % gridDim.x == blockIdx.x)
-        k_fedavg_tail<Y, X, CP, E, S, true, false, BLK>(agg, tab, K, P, nfull * (BLK * S) + threadIdx.x);
+    for (int j = 0; j < part.ntail(); ++j)
+        if (park_tail_owner(part, gridDim.x, j) == blockIdx.x)
+            k_fedavg_tail<Y, X, CP, E, S, true, false, BLK>(agg, tab, K, P, (part.ntall * HEIGHT + j) * (BLK * S) + threadIdx.x);
 }
 
-// The parked fold at any (DEPTH, SLOTS), for the probe library: a kernel template of its own, so that
-// the window kernels keep their names (profiles/pmc_traffic.json is keyed on them). The launcher
-// reports k_fedavg_pipe_win's family for it.
-template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS>
+// The parked fold at any (DEPTH, SLOTS, HEIGHT, POL), for the probe library: a kernel template of its
+// own, so that the window kernels keep their names (profiles/pmc_traffic.json is keyed on them). The
+// launcher reports k_fedavg_pipe_win's family for it.
+template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS, int DEPTH, int SLOTS, int HEIGHT = 1, int POL = 0>
 __global__ void __launch_bounds__(BLK)
 k_fedavg_park(X* __restrict__ agg, const ClientTable<typename CP::S> tab, const int K, const int64_t P, const uint32_t period,
               const uint32_t win_w) {
-    fedavg_park_body<Y, X, CP, E, S, BLK, NTS, DEPTH, SLOTS>(agg, tab, K, P, period, win_w);
+    fedavg_park_body<Y, X, CP, E, S, BLK, NTS, DEPTH, SLOTS, HEIGHT, POL>(agg, tab, K, P, period, win_w);
 }
 
 // The same fold with every wave's stores inside a chip-wide window of the GPU's 100 MHz clock
@@ -463,7 +492,7 @@ k_fedavg_pipe_win(X* __restrict__ agg, const ClientTable<typename CP::S> tab, co
                   const uint32_t period, const uint32_t win_w, const int win_mode) {
     if constexpr (PARK) {
         static_assert(INIT && !INT_FIRST && !NT && !LT && MAP == 0, "parked stores: first launches of the product geometry");
-        fedavg_park_body<Y, X, CP, E, S, BLK, NTS, kAvgParkDepth, kAvgParkSlots>(agg, tab, K, P, period, win_w);
+        fedavg_park_body<Y, X, CP, E, S, BLK, NTS, kAvgParkDepth, kAvgParkSlots, kAvgParkHeight, kAvgParkLoadPol>(agg, tab, K, P, period, win_w);
     } else {
         fedavg_pipe_body<Y, X, CP, E, S, INIT, INT_FIRST, NT, LT, BLK, NTS, MAP, true>(agg, tab, K, P, period, win_w, win_mode);
     }

@@ -13,12 +13,13 @@ constexpr bool avg_park_geometry = std::is_same<CP, CF32>::value && std::is_same
                                    std::is_same<Y, float>::value && S * E == 16 && BLK == kBlock && MAP == 0 && !LT && !NT;
 
 // Its grid: kAvgParkPerCu workgroups per CU where the occupancy query allows them (per_cu > 0: that
-// many instead), at most one per tile. Its waves never idle and keep the ring's loads in flight
+// many instead), at most one per tall or tail tile (ParkPartition::units). Its waves never idle and keep the ring's loads in flight
 // behind every consume, and more tile streams than that needs only crowd the memory system: at
 // 64 x 100 M and 2 ring buffers, 1 per CU -0.9...-1.4 % against the round-7 kernel at its own 2 per
 // CU, 2 per CU +1.4...+1.7 %, 3 per CU +4 % and more; 3 or 4 ring buffers +1.7...+6 % at every
 // grid (profiles/r08_ring_sweep.log; the round-7 kernel, whose address arithmetic drained its ring
-// before every load: profiles/r07_park_sweep.log).
+// before every load: profiles/r07_park_sweep.log). With tall tiles and nt loads, 2 per CU is still
+// +2 % (profiles/r09_height_sweep.log).
 constexpr int kAvgParkPerCu = 1;
 template <auto KERNEL, int BLK>
 int64_t avg_park_grid(int64_t ntiles, int per_cu) {
@@ -32,7 +33,7 @@ void launch_fedavg_park(X* a, const ClientTable<typename CP::S>& tab, int cnt, i
                         int per_cu, hipStream_t st) {
     constexpr int64_t kTile = (int64_t)BLK * S * E;
     constexpr auto kernel = k_fedavg_pipe_win<Y, X, CP, E, S, true, false, NT, LT, BLK, NTS, MAP, true>;
-    const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>((P + kTile - 1) / kTile, per_cu));
+    const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>(park_partition(P, kTile, kAvgParkHeight).units(), per_cu));
     g_kernel = "k_fedavg_pipe_win";
     hipLaunchKernelGGL(kernel, pgrid, dim3(BLK), 0, st, a, tab, cnt, P, period, win_w, 3);
 }
@@ -62,8 +63,20 @@ AvgWindow avg_store_window(int K, int64_t P) {
     // period and window rule (1 slot -0.9 %; 4 slots at 2.8 rounds and a 4 % window -1.4 %: both
     // within the session's noise of this one), K = 48 -1.6 %, K = 32 -2.6 % against mode 0 above.
     // K = 16 0 %, K = 8 +4 % with the round-7 kernel (profiles/r07_park_sweep.log): those keep mode 0.
+    // Tall tiles and non-temporal ring loads (kAvgParkHeight 2, kAvgParkLoadPol nt; the period is that
+    // of a round of tall tiles) — measured (profiles/r09_height_sweep.log, one process, every point
+    // bit-exact) at K = 64 x 100 M against height 1 / default policy / 2 slots: nt alone -7.0 %, height
+    // 2 alone -0.6 %, both -9.9 % (1 or 2 slots, nt or sc1 nt: within 0.2 % of each other; sc1 alone
+    // 0 %; height 4 nt -9.4 %, without nt +4.7 %; a 4 % window +2...+7 % on the 8 % one; 2 workgroups
+    // per CU +2 % on 1). Height 2, 1 slot, sc1 nt at K = 48 -9.5 %, K = 32 -4.7 %, and at the smallest
+    // pipelined model (160 MiB per client, K = 64, 5 tall tiles per workgroup) -9.4 %: no K or size at
+    // which height 1 wins, so there is no gate. 2 slots rather than 1: the same at the 8 % window and
+    // 4.7 % faster at the 4 % one, where a wave meets a closed window more often. The gain depends on
+    // the box: on two others the same setting was -4.1 and -5.0 % (nt alone -2.4 and -3.2 %), and plain
+    // bench.py against the parent commit -3.6 % at K = 64, -4.5 % at K = 48, -4.4 % at K = 32, -4.6 % at
+    // 160 MiB per client (profiles/r09_height_pairs.log).
     if constexpr (avg_park_geometry<Y, X, CP, E, S, NT, LT, BLK, NTS, MAP>) {
-        const double pperiod = 0.7 * period / 0.45 * kAvgParkPerCu / nb;
+        const double pperiod = 0.7 * period / 0.45 * kAvgParkPerCu / nb * kAvgParkHeight;   // a round of tall tiles
         if (K >= 32 && pperiod >= 500 && pperiod <= 20000) {
             w.period = (uint32_t)pperiod;
             w.w = (uint32_t)(0.08 * pperiod);

@@ -217,7 +217,7 @@ struct FedAvgCfg {
     std::atomic<int> strips{4}, unroll{0}, lanetab{0}, grid_per_cu{0}, read_per_lane{16}, block_log{8},
         sum_nostore{0}, nt_store{1}, nt{0}, fastdiv{1}, fastdiv64{1}, narrow{1}, auto_geom{1}, opt_mix{0},
         opt_win_period{0}, opt_win_w{0}, opt_win_mode{0}, opt_win_prod{0}, avg_win_period{0}, avg_win_w{0},
-        avg_win_mode{0}, avg_park_depth{0}, avg_park_slots{0};
+        avg_win_mode{0}, avg_park_depth{0}, avg_park_slots{0}, avg_park_height{0}, avg_park_loadpol{0};
 };
 FedAvgCfg g_cfg;
 int cfg_fastdiv() { return g_cfg.fastdiv.load(std::memory_order_relaxed); }
@@ -254,27 +254,37 @@ void probe_avg_window(AvgWindow& w, int& mode) {
     }
 }
 
-// AVG_PARK_DEPTH / _SLOTS on a parked launch: both 0 = the product's kernel (false); otherwise the
-// generalised one (k_fedavg_park; a knob left at 0 is 2 buffers / 1 slot), GRID n = n workgroups per
-// CU. The launcher reports the product's family for it: one fold, one name.
+// AVG_PARK_DEPTH / _SLOTS / _HEIGHT / _LOADPOL on a parked launch: all 0 = the product's kernel
+// (false); otherwise the generalised one (k_fedavg_park; a knob left at 0 is 2 buffers / 1 slot /
+// height 1 / the default policy), GRID n = n workgroups per CU. Instantiated: the nine (DEPTH, SLOTS)
+// at height 1 and the default policy; ring 2 at (HEIGHT, SLOTS) = (1, 1), (1, 2), (2, 1), (2, 2),
+// (4, 1) at every policy; ring 3 at height 2, 1 and 2 slots. Anything else launches nothing and
+// reports "k_fedavg_park (not instantiated)" as the kernel family. The launcher reports the
+// product's family for a launch: one fold, one name.
 template <typename Y, typename X, class CP, int E, int S, int BLK, int NTS>
 bool probe_fedavg_park(X* a, const ClientTable<typename CP::S>& tab, int cnt, int64_t P, uint32_t period, uint32_t win_w,
                        hipStream_t st) {
-    const int depth = g_cfg.avg_park_depth, slots = g_cfg.avg_park_slots;
-    if (!depth && !slots) return false;
+    const int depth = g_cfg.avg_park_depth, slots = g_cfg.avg_park_slots, height = g_cfg.avg_park_height;
+    const int pol = g_cfg.avg_park_loadpol;
+    if (!depth && !slots && !height && !pol) return false;
     constexpr int64_t kTile = (int64_t)BLK * S * E;
-    const int64_t ntiles = (P + kTile - 1) / kTile;
-    switch ((depth ? depth : 2) * 10 + (slots ? slots : 1)) {
-#define FA_PARK(D_, S_) \
-    case D_ * 10 + S_: { \
-        constexpr auto kernel = k_fedavg_park<Y, X, CP, E, S, BLK, NTS, D_, S_>; \
-        const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>(ntiles, cfg_grid_per_cu())); \
+    switch ((depth ? depth : 2) * 1000 + (height ? height : 1) * 100 + (slots ? slots : 1) * 10 + pol) {
+#define FA_PARK(D_, H_, S_, P_) \
+    case D_ * 1000 + H_ * 100 + S_ * 10 + P_: { \
+        constexpr auto kernel = k_fedavg_park<Y, X, CP, E, S, BLK, NTS, D_, S_, H_, P_>; \
+        const dim3 pgrid((unsigned)avg_park_grid<kernel, BLK>(park_partition(P, kTile, H_).units(), cfg_grid_per_cu())); \
         hipLaunchKernelGGL(kernel, pgrid, dim3(BLK), 0, st, a, tab, cnt, P, period, win_w); \
         break; \
     }
-        FA_PARK(2, 1) FA_PARK(2, 2) FA_PARK(2, 4) FA_PARK(3, 1) FA_PARK(3, 2) FA_PARK(3, 4) FA_PARK(4, 1) FA_PARK(4, 2) FA_PARK(4, 4)
+#define FA_PARK_POLS(D_, H_, S_) FA_PARK(D_, H_, S_, 0) FA_PARK(D_, H_, S_, 1) FA_PARK(D_, H_, S_, 2) FA_PARK(D_, H_, S_, 3)
+        FA_PARK_POLS(2, 1, 1) FA_PARK_POLS(2, 1, 2) FA_PARK_POLS(2, 2, 1) FA_PARK_POLS(2, 2, 2) FA_PARK_POLS(2, 4, 1)
+        FA_PARK(2, 1, 4, 0) FA_PARK(3, 1, 1, 0) FA_PARK(3, 1, 2, 0) FA_PARK(3, 1, 4, 0) FA_PARK(4, 1, 1, 0) FA_PARK(4, 1, 2, 0) FA_PARK(4, 1, 4, 0)
+        FA_PARK(3, 2, 1, 0) FA_PARK(3, 2, 2, 0)
+#undef FA_PARK_POLS
 #undef FA_PARK
-        default: return false;                           // (fa_tune admits no other value)
+        default:                                         // nothing runs: no other kernel stands in for a missing one
+            g_kernel = "k_fedavg_park (not instantiated)";
+            return true;
     }
     g_kernel = "k_fedavg_pipe_win";
     return true;

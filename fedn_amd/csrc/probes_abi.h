@@ -92,6 +92,10 @@ int fa_tune(int knob, int value) {
             return set(g_cfg.avg_park_depth, value, among({0, 2, 3, 4}), "parked ring depth 2, 3 or 4 (0 = the product's)");
         case FA_TUNE_AVG_PARK_SLOTS:
             return set(g_cfg.avg_park_slots, value, among({0, 1, 2, 4}), "parked tiles per workgroup 1, 2 or 4 (0 = the product's)");
+        case FA_TUNE_AVG_PARK_HEIGHT:
+            return set(g_cfg.avg_park_height, value, among({0, 1, 2, 4}), "parked tile height 1, 2 or 4 (0 = the product's)");
+        case FA_TUNE_AVG_PARK_LOADPOL:
+            return set(g_cfg.avg_park_loadpol, value, value >= 0 && value <= 3, "ring load policy 0 (default), 1 (nt), 2 (sc1) or 3 (sc1 nt)");
         default: return fail(FA_EINVAL, "fa_tune: unknown knob %d", knob);
     }
 }

@@ -106,7 +106,15 @@ enum fa_tune_knob {
                                    consume); 0 (default) = the product's. With either of the two set,
                                    the launch is k_fedavg_park's (a knob left at 0: 2 buffers, 1 slot) */,
     FA_TUNE_AVG_PARK_SLOTS = 22 /* AVG_WIN_MODE 3: parked tiles per workgroup, 1 | 2 | 4 (16 KiB of LDS
-                                   each); 0 (default) = the product's */
+                                   each); 0 (default) = the product's */,
+    FA_TUNE_AVG_PARK_HEIGHT = 23 /* AVG_WIN_MODE 3: consecutive 16 KiB tiles of the model a workgroup reads
+                                    from one client before it moves to the next client (a "tall" tile; a
+                                    parked tile is that many times 16 KiB of LDS), 1 | 2 | 4; 0 (default)
+                                    = the product's. Instantiated: ring 2 at (height, slots) = (2, 1),
+                                    (2, 2), (4, 1); ring 3 at height 2 with 1 | 2 slots; a combination
+                                    that is not instantiated launches nothing (fa_last_kernel says so) */,
+    FA_TUNE_AVG_PARK_LOADPOL = 24 /* AVG_WIN_MODE 3: cache policy of the ring's buffer loads, 0 default |
+                                     1 nt | 2 sc1 | 3 sc1 nt (ring 2, up to 2 slots at height 1) */
 };
 int fa_tune(int knob, int value);
 int64_t fa_stream_read_blocks(int64_t bytes);
