@@ -4,9 +4,9 @@
 // Included by fedagg.hip inside its anonymous namespace, after wmean_dist.h: it is that file's kernel
 // "with one extra client". This file holds the kernel and its launcher alone; from wmean_dist.h it takes the
 // tile constants (kWm*), wm_kp / wm_ck / wm_waves, WmTraits, WmTable, wm_out / wm_back, and the whole host
-// side: WmGeom and wm_geom at K + 1 tile columns, wm_workgroups, wm_fill_table, wm_for_kp and wm_finish
-// (k_wmean_finish). With C the compute type and O the output type of the dtype family (WmTraits) and
-// c_k = C(coef[k]):
+// side: WmGeom and wm_geom at K + 1 tile columns, wm_workgroups, wm_fill_table and wm_finish
+// (k_wmean_finish); the dispatch on KP is host_common.h's for_kp. With C the compute type and O the output type
+// of the dtype family (WmTraits) and c_k = C(coef[k]):
 //     v'[p] = O((C(v[p]) + c_a (C(u_a[p]) - C(v[p]))) + c_b (C(u_b[p]) - C(v[p])) + ...)
 //                                                         over the clients with c_k != 0, in index order,
 //     d[k]  = sum_p (C(u_k[p]) - C(v'[p]))^2               for every k,
@@ -202,7 +202,7 @@ int launch_cclip_dist(void* out, const void* center, double* dist, const void* c
     const bool cvec = aligned16(center);
     g_kernel = "k_cclip_dist";
     if (nwg > 0)
-        wm_for_kp(K, [&](auto kp) {
+        for_kp<8>(wm_kp(K), [&](auto kp) {                     // KP is the geometry's own wm_kp(K)
             constexpr int KP = decltype(kp)::value;
             hipLaunchKernelGGL((k_cclip_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st,
                                static_cast<O*>(out), static_cast<const O*>(center), work, tab, K, tl.live, P, gm.TE, gm.KS,

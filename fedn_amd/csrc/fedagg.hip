@@ -700,41 +700,26 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
                     void* stream) {
     g_err[0] = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!out || !updates) return fail(FA_EINVAL, "fa_trimmed_mean: null pointer argument");
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_trimmed_mean: K=%d outside 1..%d", K, kMaxK);
+    if (const int rc = check_sort_ptrs("fa_trimmed_mean", out, updates, K)) return rc;
     if (trim < 0 || 2 * trim >= K) return fail(FA_EINVAL, "fa_trimmed_mean: trim=%d leaves nothing of K=%d", trim, K);
-    if (P < 0) return fail(FA_EINVAL, "fa_trimmed_mean: negative size (P=%lld)", (long long)P);
-    const bool pair = (upd_dtype == FA_F32 && out_dtype == FA_F32) || (upd_dtype == FA_F64 && out_dtype == FA_F64) ||
-                      (upd_dtype == FA_F16 && out_dtype == FA_F16) || (upd_dtype == FA_BF16 && out_dtype == FA_F32) ||
-                      ((upd_dtype == FA_I32 || upd_dtype == FA_I64) && out_dtype == FA_F64);
-    if (!pair)
-        return fail(FA_EDTYPE, "fa_trimmed_mean: unsupported dtype pair (update %d, output %d)", upd_dtype, out_dtype);
+    if (const int rc = check_sort_size("fa_trimmed_mean", out_dtype, upd_dtype, P)) return rc;
     if (P == 0) return FA_OK;
     if (const int rc = check_updates("fa_trimmed_mean", updates, K)) return rc;
     return for_dtype(upd_dtype, [&](auto t) { return launch_order_mean<decltype(t)>(out, updates, K, trim, P, st); });
 }
 
-
 int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int keep,
                           int64_t P, void* stream) {
     g_err[0] = 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!out || !updates) return fail(FA_EINVAL, "fa_median_window_mean: null pointer argument");
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "fa_median_window_mean: K=%d outside 1..%d", K, kMaxK);
+    if (const int rc = check_sort_ptrs("fa_median_window_mean", out, updates, K)) return rc;
     if (keep < 1 || keep > K) return fail(FA_EINVAL, "fa_median_window_mean: keep=%d outside 1..K=%d", keep, K);
-    if (P < 0) return fail(FA_EINVAL, "fa_median_window_mean: negative size (P=%lld)", (long long)P);
-    const bool pair = (upd_dtype == FA_F32 && out_dtype == FA_F32) || (upd_dtype == FA_F64 && out_dtype == FA_F64) ||
-                      (upd_dtype == FA_F16 && out_dtype == FA_F16) || (upd_dtype == FA_BF16 && out_dtype == FA_F32) ||
-                      ((upd_dtype == FA_I32 || upd_dtype == FA_I64) && out_dtype == FA_F64);
-    if (!pair)
-        return fail(FA_EDTYPE, "fa_median_window_mean: unsupported dtype pair (update %d, output %d)", upd_dtype,
-                    out_dtype);
+    if (const int rc = check_sort_size("fa_median_window_mean", out_dtype, upd_dtype, P)) return rc;
     if (P == 0) return FA_OK;
     if (const int rc = check_updates("fa_median_window_mean", updates, K)) return rc;
     return for_dtype(upd_dtype,
                      [&](auto t) { return launch_median_window<decltype(t)>(out, updates, K, keep, P, st); });
 }
-
 
 int64_t fa_pairwise_sqdist_work(int K, int64_t P) {
     if (K < 1 || K > kMaxK || P < 0) return 0;

@@ -1,6 +1,8 @@
 // host_common.h — host code that more than one kernel family's launch path uses: filling a launch's
-// client table, the device's size (CUs, resident workgroups of a kernel), the robust entry points' dispatch
-// by update dtype, and the argument checks and device mappings that several entry points share.
+// client table (the fold's, and the robust kernels' table of pointers), the device's size (CUs, resident
+// workgroups of a kernel), the robust entry points' dispatch by update dtype and by padded client count, the
+// output dtype that goes with an update dtype, and the argument checks and device mappings that several entry
+// points share.
 //
 // Included by fedagg.hip inside its anonymous namespace, after the kernel headers and probes.h: it uses
 // ClientTable (fold_rules.h), the cfg_* getters (probes.h) and that file's error plumbing.
@@ -39,6 +41,17 @@ void fill_table(ClientTable<S>& t, const void* const* ptrs, const double* n, con
         t.N[j] = 0;
         t.r[j] = 0.0;
     }
+}
+
+// The K update pointers of a robust launch into its table's kMaxK entries (PairTable, OrderTable, WmTable:
+// nullptr past K); true when every one of the K is 16-byte aligned.
+bool fill_ptrs(const void* (&ptr)[kMaxK], const void* const* ups, int K) {
+    bool vec = true;
+    for (int k = 0; k < kMaxK; ++k) {
+        ptr[k] = k < K ? ups[k] : nullptr;
+        if (k < K) vec = vec && aligned16(ups[k]);
+    }
+    return vec;
 }
 
 int64_t grid_for(int64_t P, int E) {
@@ -81,10 +94,53 @@ auto for_dtype(int dtype, F&& f) {
     }
 }
 
+// f(std::integral_constant<int, KP>{}) for the padded client count of K: the power of two KP <= 64 with
+// KP / 2 < K <= KP, and MIN (2 or 8) for fewer clients. No KP below MIN is instantiated.
+template <int MIN, typename F>
+auto for_kp(int K, F&& f) {
+    static_assert(MIN == 2 || MIN == 8, "the sort and pairwise kernels start at 2, the fused distance kernels at 8");
+    if constexpr (MIN == 2) {
+        if (K <= 2) return f(std::integral_constant<int, 2>{});
+        if (K <= 4) return f(std::integral_constant<int, 4>{});
+    }
+    if (K <= 8) return f(std::integral_constant<int, 8>{});
+    if (K <= 16) return f(std::integral_constant<int, 16>{});
+    if (K <= 32) return f(std::integral_constant<int, 32>{});
+    return f(std::integral_constant<int, 64>{});
+}
+
+// The output dtype that goes with updates of `upd_dtype` in the robust rules (ops.order_mean_dtype): the float
+// dtype itself, f32 for bf16, f64 for the integers; -1 for a dtype that is none of the six.
+int order_out_dtype(int upd_dtype) {
+    switch (upd_dtype) {
+        case FA_F32: case FA_BF16: return FA_F32;
+        case FA_F16: return FA_F16;
+        case FA_F64: case FA_I32: case FA_I64: return FA_F64;
+        default: return -1;
+    }
+}
+
 // the first null among a round's K update pointers, reported in `who`'s name
 int check_updates(const char* who, const void* const* updates, int K) {
     for (int k = 0; k < K; ++k)
         if (!updates[k]) return fail(FA_EINVAL, "%s: updates[%d] is NULL", who, k);
+    return FA_OK;
+}
+
+// The argument checks of the two sort entry points (fa_trimmed_mean, fa_median_window_mean), reported in
+// `who`'s name, in two halves: the entry point's own bound on its count (trim, keep) is refused between them,
+// after a bad K and before a bad P, as it always was.
+int check_sort_ptrs(const char* who, const void* out, const void* const* updates, int K) {
+    if (!out || !updates) return fail(FA_EINVAL, "%s: null pointer argument", who);
+    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "%s: K=%d outside 1..%d", who, K, kMaxK);
+    return FA_OK;
+}
+
+int check_sort_size(const char* who, int out_dtype, int upd_dtype, int64_t P) {
+    if (P < 0) return fail(FA_EINVAL, "%s: negative size (P=%lld)", who, (long long)P);
+    const int want = order_out_dtype(upd_dtype);
+    if (want < 0 || out_dtype != want)
+        return fail(FA_EDTYPE, "%s: unsupported dtype pair (update %d, output %d)", who, upd_dtype, out_dtype);
     return FA_OK;
 }
 

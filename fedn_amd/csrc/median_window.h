@@ -2,7 +2,8 @@
 // (fa_median_window_mean), Bulyan's second stage.
 //
 // Included by fedagg.hip inside its anonymous namespace, after order_mean.h: the keys, the comparator
-// network, OrderTraits, OrderTable, order_vec_elems and the strip loads / stores are that header's. With
+// network, OrderTraits, OrderTable, order_vec_elems, the launch path (launch_sort_kernel) and the strip loads /
+// stores are that header's. With
 // FA_ORDER_NET_ONLY defined only the window-start functions are compiled, by any C++17 compiler (after
 // order_mean.h under the same guard, for FA_ORDER_HD): tests/test_bulyan_host.py checks them against the
 // oracle on the CPU.
@@ -135,39 +136,14 @@ k_median_window(typename OrderTraits<T>::O* __restrict__ out, const OrderTable t
         for (int e = 0; e < rem; ++e) out[i0 + e] = r[e];
 }
 
-template <typename T, int KP>
-int launch_median_window_kp(void* out, const OrderTable& tab, int K, int keep, int64_t P, bool vec, hipStream_t st) {
-    using O = typename OrderTraits<T>::O;
-    constexpr int EV = order_vec_elems<typename OrderTraits<T>::KEY, KP>();   // k_order_mean's (§3.11's table)
-    O* o = static_cast<O*>(out);
-    if (vec && EV > 1) {
-        const dim3 grid((unsigned)grid_for(P, EV));
-        hipLaunchKernelGGL((k_median_window<T, KP, EV>), grid, dim3(kBlock), 0, st, o, tab, K, keep, P);
-    } else {
-        const dim3 grid((unsigned)grid_for(P, 1));
-        hipLaunchKernelGGL((k_median_window<T, KP, 1>), grid, dim3(kBlock), 0, st, o, tab, K, keep, P);
-    }
-    return check_launch("fa_median_window_mean: kernel launch");
-}
-
 template <typename T>
 int launch_median_window(void* out, const void* const* ups, int K, int keep, int64_t P, hipStream_t st) {
-    // grid = ceil(P / E / 256) workgroups must fit the 32-bit grid dimension
-    if (P > (int64_t)0x7FFFFFFF * kBlock)
-        return fail(FA_EINVAL, "fa_median_window_mean: P=%lld is too large", (long long)P);
-    OrderTable tab;
-    bool vec = aligned16(out);
-    for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
-        if (k < K) vec = vec && aligned16(ups[k]);
-    }
-    g_kernel = "k_median_window";
-    if (K <= 2) return launch_median_window_kp<T, 2>(out, tab, K, keep, P, vec, st);
-    if (K <= 4) return launch_median_window_kp<T, 4>(out, tab, K, keep, P, vec, st);
-    if (K <= 8) return launch_median_window_kp<T, 8>(out, tab, K, keep, P, vec, st);
-    if (K <= 16) return launch_median_window_kp<T, 16>(out, tab, K, keep, P, vec, st);
-    if (K <= 32) return launch_median_window_kp<T, 32>(out, tab, K, keep, P, vec, st);
-    return launch_median_window_kp<T, 64>(out, tab, K, keep, P, vec, st);
+    auto launch = [&](auto kp, auto e, dim3 grid, auto* o, const OrderTable& tab) {      // E is k_order_mean's (§3.11)
+        g_kernel = "k_median_window";
+        hipLaunchKernelGGL((k_median_window<T, decltype(kp)::value, decltype(e)::value>), grid, dim3(kBlock), 0, st, o, tab,
+                           K, keep, P);
+    };
+    return launch_sort_kernel<T>("fa_median_window_mean", out, ups, K, P, launch);
 }
 
 #endif  // FA_ORDER_NET_ONLY

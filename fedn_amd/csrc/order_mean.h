@@ -1,8 +1,10 @@
 // order_mean.h — coordinate-wise trimmed mean / median over K client buffers (fa_trimmed_mean).
 //
 // Included by fedagg.hip inside its anonymous namespace (it uses fold_rules.h's element types and strip
-// loads / stores, host_common.h's grid_for and that file's error plumbing). With FA_ORDER_NET_ONLY defined only the comparator network is
-// compiled, by any C++17 compiler: tests/test_robust_host.py checks it with the 0-1 principle.
+// loads / stores, host_common.h's grid_for, fill_ptrs and for_kp, and that file's error plumbing). Its launch
+// path, launch_sort_kernel, also serves median_window.h's kernel. With FA_ORDER_NET_ONLY defined only the
+// comparator network is compiled, by any C++17 compiler: tests/test_robust_host.py checks it with the 0-1
+// principle.
 //
 // Per element: the K values become unsigned keys whose integer order is the rule's total order
 // (-0 before +0, every NaN after +inf, all NaNs equal), the keys are sorted by a fully unrolled
@@ -174,38 +176,35 @@ template <typename KEY, int KP> constexpr int order_vec_elems() {
     return KP <= 16 ? 2 : 1;
 }
 
-template <typename T, int KP>
-int launch_order_mean_kp(void* out, const OrderTable& tab, int K, int trim, int64_t P, bool vec, hipStream_t st) {
-    using O = typename OrderTraits<T>::O;
-    constexpr int EV = order_vec_elems<typename OrderTraits<T>::KEY, KP>();
-    O* o = static_cast<O*>(out);
-    if (vec && EV > 1) {
-        const dim3 grid((unsigned)grid_for(P, EV));
-        hipLaunchKernelGGL((k_order_mean<T, KP, EV>), grid, dim3(kBlock), 0, st, o, tab, K, trim, P);
-    } else {
-        const dim3 grid((unsigned)grid_for(P, 1));
-        hipLaunchKernelGGL((k_order_mean<T, KP, 1>), grid, dim3(kBlock), 0, st, o, tab, K, trim, P);
-    }
-    return check_launch("fa_trimmed_mean: kernel launch");
+// The launch path of the two sort kernels, k_order_mean and median_window.h's k_median_window, reported in the
+// entry point `who`'s name: the bound on P, the client table, the padded client count KP and the elements a
+// lane, E (order_vec_elems when out and every update are 16-byte aligned, else 1).
+// launch(kp, e, grid, out, tab) launches the <T, KP, E> instantiation; kp and e are std::integral_constant tags.
+template <typename T, typename LAUNCH>
+int launch_sort_kernel(const char* who, void* out, const void* const* ups, int K, int64_t P, LAUNCH&& launch) {
+    // grid = ceil(P / E / 256) workgroups must fit the 32-bit grid dimension
+    if (P > (int64_t)0x7FFFFFFF * kBlock) return fail(FA_EINVAL, "%s: P=%lld is too large", who, (long long)P);
+    OrderTable tab;
+    const bool vec = fill_ptrs(tab.ptr, ups, K) && aligned16(out);
+    auto* o = static_cast<typename OrderTraits<T>::O*>(out);
+    for_kp<2>(K, [&](auto kp) {
+        constexpr int EV = order_vec_elems<typename OrderTraits<T>::KEY, decltype(kp)::value>();
+        if (vec && EV > 1) launch(kp, std::integral_constant<int, EV>{}, dim3((unsigned)grid_for(P, EV)), o, tab);
+        else launch(kp, std::integral_constant<int, 1>{}, dim3((unsigned)grid_for(P, 1)), o, tab);
+    });
+    char what[64];
+    std::snprintf(what, sizeof(what), "%s: kernel launch", who);
+    return check_launch(what);
 }
 
 template <typename T>
 int launch_order_mean(void* out, const void* const* ups, int K, int trim, int64_t P, hipStream_t st) {
-    // grid = ceil(P / E / 256) workgroups must fit the 32-bit grid dimension
-    if (P > (int64_t)0x7FFFFFFF * kBlock) return fail(FA_EINVAL, "fa_trimmed_mean: P=%lld is too large", (long long)P);
-    OrderTable tab;
-    bool vec = aligned16(out);
-    for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
-        if (k < K) vec = vec && aligned16(ups[k]);
-    }
-    g_kernel = "k_order_mean";
-    if (K <= 2) return launch_order_mean_kp<T, 2>(out, tab, K, trim, P, vec, st);
-    if (K <= 4) return launch_order_mean_kp<T, 4>(out, tab, K, trim, P, vec, st);
-    if (K <= 8) return launch_order_mean_kp<T, 8>(out, tab, K, trim, P, vec, st);
-    if (K <= 16) return launch_order_mean_kp<T, 16>(out, tab, K, trim, P, vec, st);
-    if (K <= 32) return launch_order_mean_kp<T, 32>(out, tab, K, trim, P, vec, st);
-    return launch_order_mean_kp<T, 64>(out, tab, K, trim, P, vec, st);
+    auto launch = [&](auto kp, auto e, dim3 grid, auto* o, const OrderTable& tab) {
+        g_kernel = "k_order_mean";
+        hipLaunchKernelGGL((k_order_mean<T, decltype(kp)::value, decltype(e)::value>), grid, dim3(kBlock), 0, st, o, tab, K,
+                           trim, P);
+    };
+    return launch_sort_kernel<T>("fa_trimmed_mean", out, ups, K, P, launch);
 }
 
 #endif  // FA_ORDER_NET_ONLY

@@ -1,9 +1,9 @@
 // pair_dist.h — pairwise squared distances of K client buffers (fa_pairwise_sqdist, kernel k_pair_sqdist).
 //
-// Included by fedagg.hip inside its anonymous namespace (it uses fold_rules.h's element types and that file's
-// error plumbing). D[i][j] = sum_p (C(u_i[p]) - C(u_j[p]))^2 in the compute type C of the dtype family:
-// f32 for f32 / f16 / bf16 (widened exactly), f64 for f64 / i32 / i64 (one rounding). DESIGN.md §3.8 has
-// the definition, the error bound and the resource table.
+// Included by fedagg.hip inside its anonymous namespace (it uses fold_rules.h's element types, host_common.h's
+// fill_ptrs and for_kp, and that file's error plumbing). D[i][j] = sum_p (C(u_i[p]) - C(u_j[p]))^2 in the
+// compute type C of the dtype family: f32 for f32 / f16 / bf16 (widened exactly), f64 for f64 / i32 / i64 (one
+// rounding). DESIGN.md §3.8 has the definition, the error bound and the resource table.
 //
 // Shape: a workgroup stages a tile of TE elements x KP clients in LDS, converted to C, element-major
 // (one padded row of KP values per element). A lane owns one B x B block (bi <= bj) of the client-pair
@@ -293,12 +293,7 @@ inline int pair_family(int dtype) {
 // f(PairGeom-carrying tag) for the (family, KP) of (dtype, K)
 template <typename C, typename F>
 int pair_for_kp(int K, F&& f) {
-    if (K <= 2) return f(PairGeom<C, 2>{});
-    if (K <= 4) return f(PairGeom<C, 4>{});
-    if (K <= 8) return f(PairGeom<C, 8>{});
-    if (K <= 16) return f(PairGeom<C, 16>{});
-    if (K <= 32) return f(PairGeom<C, 32>{});
-    return f(PairGeom<C, 64>{});
+    return for_kp<2>(K, [&](auto kp) -> int { return f(PairGeom<C, decltype(kp)::value>{}); });
 }
 
 inline int64_t pair_workgroups(int64_t P, int TE) {
@@ -309,11 +304,7 @@ template <typename C>
 int launch_pair_sqdist(double* D, const void* const* ups, int dtype, int K, int64_t P, int accumulate, double* work,
                        hipStream_t st) {
     PairTable tab;
-    bool vec = true;
-    for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
-        if (k < K) vec = vec && aligned16(ups[k]);
-    }
+    const bool vec = fill_ptrs(tab.ptr, ups, K);
     g_kernel = "k_pair_sqdist";
     return pair_for_kp<C>(K, [&](auto gm) -> int {
         using GM = decltype(gm);

@@ -2,9 +2,10 @@
 // (fa_weighted_mean_sqdist, kernel k_wmean_dist): one smoothed Weiszfeld step of the geometric median.
 //
 // Included by fedagg.hip inside its anonymous namespace, after pair_dist.h (it uses that file's
-// conversions, 16-byte loads and fused multiply-add, fold_rules.h's element types, host_common.h's for_dtype and
-// fedagg.hip's error plumbing). Its host side — geometry, table builder, KP dispatch, the finishing launch and
-// the step entry points' argument checks — also serves cclip.h's kernel.
+// conversions, 16-byte loads and fused multiply-add, fold_rules.h's element types, host_common.h's for_dtype,
+// for_kp, fill_ptrs and order_out_dtype, and fedagg.hip's error plumbing). Its host side — geometry, table
+// builder, the finishing launch and the step entry points' argument checks — also serves cclip.h's kernel; the
+// two kernels' bodies stay two copies (DESIGN.md §3.10 has the two attempts at one and their figures).
 // With C the compute type of the dtype family (f32 for f32 / f16 / bf16, f64 for f64 / i32 / i64) and
 // b_k = C(beta[k]):
 //     z[p] = O(((b_a C(u_a[p]) + b_b C(u_b[p])) + ...))   over the clients with b_k != 0, in index order,
@@ -257,28 +258,14 @@ struct WmLive {
 
 template <typename C>
 WmLive wm_fill_table(WmTable<C>& tab, const void* const* ups, const double* bc, int K, bool skip_first) {
-    WmLive r{true, 0};
+    WmLive r{fill_ptrs(tab.ptr, ups, K), 0};
     for (int k = 0; k < kMaxK; ++k) {
-        tab.ptr[k] = k < K ? ups[k] : nullptr;
         tab.b[k] = k < K ? (C)bc[k] : C(0);
-        if (k >= K) continue;
-        r.vec = r.vec && aligned16(ups[k]);
-        if (bc[k] == 0.0) continue;
+        if (k >= K || bc[k] == 0.0) continue;
         if (skip_first) skip_first = false;
         else r.live |= 1ull << k;
     }
     return r;
-}
-
-// f(std::integral_constant<int, KP>) for the padded client count of K
-template <typename F>
-void wm_for_kp(int K, F&& f) {
-    switch (wm_kp(K)) {
-        case 8: f(std::integral_constant<int, 8>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        default: f(std::integral_constant<int, 64>{}); break;
-    }
 }
 
 // the launch that follows either distance kernel: dist[k] from the nwg partials; `who` names the failed launch
@@ -298,7 +285,7 @@ inline int wm_check_step(const char* who, const char* cname, const char* gives, 
     if (P < 0) return fail(FA_EINVAL, "%s: negative size (P=%lld)", who, (long long)P);
     const int fam = pair_family(upd_dtype);
     if (!fam) return fail(FA_EDTYPE, "%s: unsupported dtype %d", who, upd_dtype);
-    const int want = upd_dtype == FA_F32 || upd_dtype == FA_BF16 ? FA_F32 : (upd_dtype == FA_F16 ? FA_F16 : FA_F64);
+    const int want = order_out_dtype(upd_dtype);
     if (out_dtype != want)
         return fail(FA_EDTYPE, "%s: updates of dtype %d %s of dtype %d, not %d", who, upd_dtype, gives, want, out_dtype);
     for (int k = 0; k < K; ++k) {
@@ -322,7 +309,7 @@ int launch_wmean_dist(void* out, double* dist, const void* const* ups, const dou
     const int nwg = (int)wm_workgroups(P, gm);
     g_kernel = "k_wmean_dist";
     if (nwg > 0)
-        wm_for_kp(K, [&](auto kp) {
+        for_kp<8>(wm_kp(K), [&](auto kp) {                     // KP is the geometry's own wm_kp(K)
             constexpr int KP = decltype(kp)::value;
             hipLaunchKernelGGL((k_wmean_dist<T, KP, wm_ck(KP)>), dim3((unsigned)nwg), dim3(kBlock), 0, st,
                                static_cast<O*>(out), work, tab, K, kfirst, tl.live, P, gm.TE, gm.KS, gm.FT, (int)tl.vec);

@@ -212,7 +212,7 @@ def test_ops_every_workgroup_two_tiles_and_a_ragged_one(name):
     _check_d(_z(d), cr.dists(S[:, :P], zw), ops.sqdist_rtol(TORCH_DT[name], P), f"{name} K={K} P={P}")
 
 
-@pytest.mark.parametrize("name,K", [("f16", 33), ("i32", 33)])
+@pytest.mark.parametrize("name,K", [("f16", 33), ("bf16", 33), ("i32", 33)])
 def test_ops_chains_flushed_mid_kernel(name, K):
     """A size at which every workgroup walks more tiles than one flush period, so the chains are flushed
     to f64 in mid-kernel as well as at the end. The updates are constants (client k holds k / 2; k for

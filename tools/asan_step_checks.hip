@@ -6,7 +6,8 @@
 //         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -Xarch_host -fno-omit-frame-pointer -o /tmp/step_checks asan_step_checks.hip
 //     ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 /tmp/step_checks
-// profiles/r18_bulyan_asan_host.log is its output (r17_hostfold_asan_host.log: before fa_median_window_mean).
+// profiles/r21_distbody_asan_host.log is its output (r18_bulyan_asan_host.log: before fa_trimmed_mean's refusals
+// and the pointer-table fill; r17_hostfold_asan_host.log: before fa_median_window_mean).
 #include "../fedn_amd/csrc/fedagg.hip"
 
 #include <cstdlib>
@@ -89,7 +90,28 @@ int main() {
            FA_EINVAL, "fa_centered_clip_step: updates[4] is NULL");
     expect("wmean accumulate, P=0 (null updates pass)",
            fa_weighted_mean_sqdist(nullptr, FA_F64, dist, ups, FA_I64, beta, K, 0, 1, work, nullptr), FA_OK, nullptr);
+    // the two sort entry points share one check (check_sort_ptrs, check_sort_size): every refusal under both names
     expect("trimmed mean P=0", fa_trimmed_mean(out, FA_F32, ups, FA_BF16, K, 1, 0, nullptr), FA_OK, nullptr);
+    expect("trimmed mean null out", fa_trimmed_mean(nullptr, FA_F32, ups, FA_F32, K, 1, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: null pointer argument");
+    expect("trimmed mean null updates", fa_trimmed_mean(out, FA_F32, nullptr, FA_F32, K, 1, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: null pointer argument");
+    expect("trimmed mean K=0", fa_trimmed_mean(out, FA_F32, ups, FA_F32, 0, 0, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: K=0 outside 1..64");
+    expect("trimmed mean K=65", fa_trimmed_mean(out, FA_F32, ups, FA_F32, 65, 1, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: K=65 outside 1..64");
+    expect("trimmed mean trim=-1", fa_trimmed_mean(out, FA_F32, ups, FA_F32, K, -1, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: trim=-1 leaves nothing of K=5");
+    expect("trimmed mean 2 trim > K", fa_trimmed_mean(out, FA_F32, ups, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: trim=3 leaves nothing of K=5");
+    expect("trimmed mean P<0", fa_trimmed_mean(out, FA_F32, ups, FA_F32, K, 1, -1, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: negative size (P=-1)");
+    expect("trimmed mean dtype pair", fa_trimmed_mean(out, FA_F64, ups, FA_F32, K, 1, 64, nullptr), FA_EDTYPE,
+           "fa_trimmed_mean: unsupported dtype pair (update 0, output 1)");
+    expect("trimmed mean dtype 99 / -1", fa_trimmed_mean(out, -1, ups, 99, K, 1, 64, nullptr), FA_EDTYPE,
+           "fa_trimmed_mean: unsupported dtype pair (update 99, output -1)");
+    expect("trimmed mean updates[4] null", fa_trimmed_mean(out, FA_F32, ups, FA_F32, K, 1, 64, nullptr), FA_EINVAL,
+           "fa_trimmed_mean: updates[4] is NULL");
     expect("median window null out", fa_median_window_mean(nullptr, FA_F32, ups, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
            "fa_median_window_mean: null pointer argument");
     expect("median window null updates", fa_median_window_mean(out, FA_F32, nullptr, FA_F32, K, 3, 64, nullptr), FA_EINVAL,
@@ -124,6 +146,23 @@ int main() {
         const bool ok = a.live == 0x18ull && b.live == 0x1Aull && a.vec && tab.ptr[5] == nullptr && tab.b[3] == 0.25f;
         std::printf("%s table builder: live (first skipped) %#llx, live %#llx\n", ok ? "ok  " : "FAIL", a.live, b.live);
         if (!ok) ++g_bad;
+    }
+    // the pointer-table fill on exactly-sized heap arrays: K entries read, kMaxK written
+    {
+        const void** five = (const void**)std::malloc(K * sizeof(void*));
+        PairTable* pt = (PairTable*)std::malloc(sizeof(PairTable));
+        for (int k = 0; k < K; ++k) five[k] = buf + 64 * k;
+        const bool all = fill_ptrs(pt->ptr, five, K);
+        five[2] = buf + 1;
+        const bool odd = fill_ptrs(pt->ptr, five, K);
+        const bool none = fill_ptrs(pt->ptr, five, 0);
+        const bool ok = all == ((reinterpret_cast<uintptr_t>(buf) & 15u) == 0) && !odd && none && pt->ptr[0] == nullptr &&
+                        pt->ptr[kMaxK - 1] == nullptr;
+        std::printf("%s pointer-table fill: aligned %d, one odd pointer %d, K = 0 %d\n", ok ? "ok  " : "FAIL", (int)all,
+                    (int)odd, (int)none);
+        if (!ok) ++g_bad;
+        std::free(five);
+        std::free(pt);
     }
     // work sizes: the f64 geometry is the largest of the six at every (K, P) tried
     {
