@@ -664,7 +664,12 @@ int fa_host_register(void* p, int64_t bytes) {
     g_err[0] = 0;
     if (!p || bytes <= 0) return fail(FA_EINVAL, "fa_host_register: bad arguments");
     hipError_t e = hipHostRegister(p, (size_t)bytes, hipHostRegisterPortable);
-    if (e != hipSuccess) return fail(FA_EHIP, "fa_host_register: %s", hipGetErrorString(e));
+    if (e != hipSuccess) {
+        // refused (not every platform page-locks memory the caller mapped): callers go on without
+        // it, and the next launch's hipGetLastError must not report this
+        (void)hipGetLastError();
+        return fail(FA_EHIP, "fa_host_register: %s", hipGetErrorString(e));
+    }
     return FA_OK;
 }
 

@@ -561,7 +561,8 @@ class HostGather:
     ``posix_fallocate``: a full /dev/shm raises here, not as a fault later), every rank of the node
     maps it and page-locks its mapping (``fa_host_register``) once, and the file's name is removed as
     soon as all ranks hold it, so nothing outlives the processes. :meth:`gather` then costs one
-    D2H per rank plus a barrier, all links at once.
+    D2H per rank plus a barrier, all links at once (plus one host copy per rank where the mapping
+    cannot be page-locked: :meth:`_pin`).
     """
 
     def __init__(self, P, dtype, bounds, group=None, dst=0, shm_dir="/dev/shm"):
@@ -599,14 +600,27 @@ class HostGather:
             os.unlink(name[0])
         self.pinned = False
         self._stream = None
+        self._bounce = None
 
     def _pin(self, device):
+        """Page-lock the mapping for ``device``'s DMA, once. Where the platform refuses that (some
+        virtual machines page-lock only memory the runtime allocated), the slices are D2H'd into a
+        pinned block of this rank's own (:meth:`_through`) and the host copies them into the mapping."""
         from . import ops
-        if not self.pinned:
+        if self._stream is None:
             with torch.cuda.device(device):
-                ops.host_register(self.host)
-            self.pinned = True
+                try:
+                    ops.host_register(self.host)
+                    self.pinned = True
+                except ops.FedAggError:
+                    pass
             self._stream = torch.cuda.Stream(device)
+
+    def _through(self, n):
+        """The pinned block of at least ``n`` elements that stands in for an unpinned mapping."""
+        if self._bounce is None or self._bounce.numel() < n:
+            self._bounce = torch.empty(n, dtype=self.dtype, pin_memory=True)
+        return self._bounce
 
     def gather(self, local, pieces=None):
         """``local``: this rank's part of the model (device or CPU tensor). ``pieces``: where it goes,
@@ -635,9 +649,15 @@ class HostGather:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(local.device))
                 self._stream.wait_event(ev)
+                # an unpinned mapping: through the pinned block, laid out as ``local`` is
+                via = None if self.pinned else self._through(local.numel())
                 for lo, hi, l0 in pieces:
-                    ops.copy_async(self.host.data_ptr() + lo * es, local[l0:], (hi - lo) * es, self._stream)
+                    dst = self.host.data_ptr() + lo * es if via is None else via.data_ptr() + l0 * es
+                    ops.copy_async(dst, local[l0:], (hi - lo) * es, self._stream)
                 self._stream.synchronize()
+                if via is not None:
+                    for lo, hi, l0 in pieces:
+                        self.host[lo:hi].copy_(via[l0:l0 + hi - lo])
             else:
                 for lo, hi, l0 in pieces:
                     self.host[lo:hi].copy_(local[l0:l0 + hi - lo])

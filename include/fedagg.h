@@ -327,6 +327,8 @@ int fa_cast(void* out, int out_dtype, const void* in, int in_dtype, int ndim, co
  *                    already enabled is not an error
  * fa_host_register   page-lock host memory the caller mapped (the node's shared host model that
  *                    every rank D2H's its slice into: sharded.HostGather), so DMA reaches it directly;
+ *                    FA_EHIP where the platform refuses (some virtual machines page-lock only what
+ *                    the runtime allocates): the caller then copies through pinned memory of its own
  * fa_host_unregister undo it before the caller unmaps
  * fa_host_device_ptr the device address of page-locked host memory (hipHostGetDevicePointer): a
  *                    small round's fold reads its clients from the pinned arena and writes the

@@ -25,6 +25,20 @@ def _slice(monkeypatch):
     monkeypatch.setattr(layout, "MULTIDEV_MIN_BYTES", 0)
 
 
+@pytest.fixture(scope="module")
+def can_register():
+    """Whether this platform page-locks memory the process already holds (hipHostRegister): some
+    virtual machines page-lock only what the runtime allocates itself."""
+    from fedn_amd import ops
+    a = np.zeros(1 << 20, dtype=np.uint8)
+    try:
+        ops.host_register_ptr(a.ctypes.data, a.nbytes)
+    except ops.FedAggError:
+        return False
+    ops.host_unregister_ptr(a.ctypes.data)
+    return True
+
+
 def _clients(rng, base, K, pinned=False):
     from fedn_amd.helper import pinned_empty
     ups = [[(b + 0.01 * rng.standard_normal(b.shape)).astype(np.float32) for b in base] for _ in range(K)]
@@ -104,9 +118,11 @@ def test_sharded_fedavg_host_updates_pinned(ndev, mode):
 
 @pytest.mark.parametrize("ndev", [2, 3])
 @pytest.mark.parametrize("share", [False, True], ids=["distinct", "shared_arrays"])
-def test_sharded_fedavg_host_updates_in_place(ndev, share, monkeypatch):
+def test_sharded_fedavg_host_updates_in_place(ndev, share, monkeypatch, can_register):
     """INPLACE_REGISTER: pageable arrays page-locked in place. ``shared_arrays``: two clients hand
     over the very same array objects — registered once, DMA'd for both; the model is the same."""
+    if not can_register:
+        pytest.skip("hipHostRegister is not supported here")
     from fedn_amd import multidev, ops
     monkeypatch.setattr(multidev, "INPLACE_REGISTER", True)
     from fedn_amd.aggregators.fedavg import Aggregator
@@ -135,8 +151,55 @@ def test_sharded_fedavg_host_updates_in_place(ndev, share, monkeypatch):
     torch.cuda.synchronize()
 
 
+def test_refused_registration_packs_and_leaves_no_error_behind(monkeypatch):
+    """A registration the runtime refuses (here: of pages that are registered already; on a platform
+    without hipHostRegister: any) is a FedAggError for its caller and nothing else: the launches
+    after it do not report it, and an INPLACE_REGISTER round whose registrations are all refused
+    packs every byte and gives the same model."""
+    from fedn_amd import _abi, multidev, ops
+    from fedn_amd.aggregators.fedavg import Aggregator
+    from fedn_amd.updatehandler import MemoryUpdateHandler
+    a = np.zeros(1 << 20, dtype=np.uint8)
+    registered = False
+    try:
+        for _ in range(2):
+            try:
+                ops.host_register_ptr(a.ctypes.data, a.nbytes)
+                registered = True
+            except ops.FedAggError:
+                pass
+        x = torch.full((4099,), 3.0, device=DEV)
+        out = torch.empty_like(x)
+        ops.fedavg_fold(out, [x, x], [1, 1], [1, 2], init=True)
+        assert bool((out == 3.0).all())
+    finally:
+        if registered:
+            ops.host_unregister_ptr(a.ctypes.data)
+
+    def refuse(ptr, nbytes):
+        raise ops.FedAggError(_abi.FA_EHIP, "fa_host_register: refused")
+
+    monkeypatch.setattr(multidev, "INPLACE_REGISTER", True)
+    monkeypatch.setattr(multidev.ops, "host_register_ptr", refuse)
+    rng = np.random.default_rng(99)
+    base = [rng.standard_normal(s).astype(np.float32) for s in SHAPES]
+    ups, ns = _clients(rng, base, 3)
+    uh = MemoryUpdateHandler()
+    agg = Aggregator(uh, devices=[DEV, DEV])
+    for u, n in zip(ups, ns):
+        uh.submit(u, n)
+    model, data = agg.combine_models(helper=None)
+    want, nr = ref.fedavg_combine(list(zip(ups, ns)))
+    assert data["nr_aggregated_models"] == nr == 3
+    assert_lists_identical(model, want, "refused registrations: packed")
+    assert data["bytes_h2d_in_place"] == 0
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("pinned", [False, True], ids=["registered", "pinned"])
-def test_sharded_fedopt_host_updates_in_place(pinned, monkeypatch):
+def test_sharded_fedopt_host_updates_in_place(pinned, monkeypatch, can_register):
+    if not pinned and not can_register:
+        pytest.skip("hipHostRegister is not supported here")
     from fedn_amd import multidev
     from fedn_amd.aggregators.fedopt import Aggregator
     monkeypatch.setattr(multidev, "INPLACE_REGISTER", not pinned)

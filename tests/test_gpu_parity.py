@@ -1579,6 +1579,37 @@ def test_p2p_allgather_gloo_hip(world, P, chunk, double, engine):
     _check_p2p_results(res, want, want2, want3, engine)
 
 
+@pytest.mark.parametrize("refused", [False, True], ids=["page_locked_if_possible", "registration_refused"])
+def test_host_gather_device_pieces(refused, monkeypatch):
+    """HostGather.gather of device pieces (block-cyclic: several pieces at local offsets, a ragged
+    last one) into the shared host model, with the mapping page-locked where the platform does that
+    and with the registration refused (the pieces then go through a pinned block of the rank's own):
+    the same bytes; a second gather of a longer local buffer regrows that block."""
+    from fedn_amd import _abi, ops
+    from fedn_amd.sharded import HostGather
+    if refused:
+        def refuse(t):
+            raise _abi.FedAggError(_abi.FA_EHIP, "fa_host_register: refused")
+        monkeypatch.setattr(ops, "host_register", refuse)
+    P = 10_007
+    hg = HostGather(P, torch.float32, [(0, P)])
+    try:
+        for n, pieces in ((6_000, [(0, 3000, 0), (7000, 10_007, 2993)]),
+                          (8_200, [(4096, 8192, 0), (0, 4096, 4100)])):
+            local = torch.randn(n, generator=torch.Generator(device=DEV).manual_seed(n), device=DEV)
+            hg.host.fill_(float("nan"))
+            got = hg.gather(local, pieces=pieces)
+            want = torch.full((P,), float("nan"))
+            for lo, hi, l0 in pieces:
+                want[lo:hi] = local[l0:l0 + hi - lo].cpu()
+            assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+            assert not (refused and hg.pinned)
+        with pytest.raises(ValueError, match="outside"):
+            hg.gather(local, pieces=[(0, 8201, 0)])
+    finally:
+        hg.close()
+
+
 @pytest.mark.parametrize("K", [1, 3, 9, 64, 70])
 @pytest.mark.parametrize("P,ndst", [(1, 1), (4099, 0), (4099, 3), (1_000_003, 7)])
 def test_fedavg_fold_push(K, P, ndst):
