@@ -140,6 +140,13 @@ EXPORTS = {
         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,   # out (or NULL), out_dtype, carry_out, carry_in (or NULL)
         ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,    # center, updates, upd_dtype
         ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),   # coef, K, P, stream
+    "fa_order_mean_wide_work": (ctypes.c_size_t, [ctypes.c_int]),                  # K
+    "fa_order_mean_wide_tile": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),       # upd_dtype, K
+    "fa_order_mean_wide": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
+        ctypes.c_int, ctypes.c_int, ctypes.c_int64,          # K, trim, P
+        ctypes.c_void_p, ctypes.c_void_p]),                  # work, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -163,7 +170,7 @@ PROBE_EXPORTS = {
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

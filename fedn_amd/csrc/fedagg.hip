@@ -90,6 +90,7 @@ size_t dt_size(int dt) {
 #include "fedavg_launch.h"    // store window, parked grid, geometry by size, launch_fedavg
 #include "fedopt_launch.h"    // store window, launch_fedopt
 #include "order_mean.h"       // coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
+#include "order_wide.h"       // the same rule for up to 1024 clients, a wavefront a coordinate (k_order_wide, fa_order_mean_wide)
 #include "median_window.h"    // mean of the values closest to the median, Bulyan (k_median_window, fa_median_window_mean)
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
@@ -711,6 +712,29 @@ int fa_trimmed_mean(void* out, int out_dtype, const void* const* updates, int up
     if (P == 0) return FA_OK;
     if (const int rc = check_updates("fa_trimmed_mean", updates, K)) return rc;
     return for_dtype(upd_dtype, [&](auto t) { return launch_order_mean<decltype(t)>(out, updates, K, trim, P, st); });
+}
+
+size_t fa_order_mean_wide_work(int K) { return (K < 1 || K > kMaxWideK) ? 0 : (size_t)K * sizeof(void*); }
+
+int fa_order_mean_wide_tile(int upd_dtype, int K) {
+    if (K < 1 || K > kMaxWideK || order_out_dtype(upd_dtype) < 0) return 0;
+    return for_dtype(upd_dtype, [&](auto t) {
+        return for_wide_kp(K, [](auto kp) -> int { return WideGeom<decltype(t), decltype(kp)::value>::C; });
+    });
+}
+
+int fa_order_mean_wide(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int trim, int64_t P,
+                       void* work, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (const int rc = check_sort_ptrs("fa_order_mean_wide", out, updates, K, kMaxWideK)) return rc;
+    if (!work) return fail(FA_EINVAL, "fa_order_mean_wide: work is NULL");
+    if (trim < 0 || 2 * trim >= K) return fail(FA_EINVAL, "fa_order_mean_wide: trim=%d leaves nothing of K=%d", trim, K);
+    if (const int rc = check_sort_size("fa_order_mean_wide", out_dtype, upd_dtype, P)) return rc;
+    if (P == 0) return FA_OK;
+    if (const int rc = check_updates("fa_order_mean_wide", updates, K)) return rc;
+    return for_dtype(upd_dtype,
+                     [&](auto t) { return launch_order_wide<decltype(t)>(out, updates, K, trim, P, work, st); });
 }
 
 int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int keep,

@@ -127,12 +127,12 @@ int check_updates(const char* who, const void* const* updates, int K) {
     return FA_OK;
 }
 
-// The argument checks of the two sort entry points (fa_trimmed_mean, fa_median_window_mean), reported in
-// `who`'s name, in two halves: the entry point's own bound on its count (trim, keep) is refused between them,
-// after a bad K and before a bad P, as it always was.
-int check_sort_ptrs(const char* who, const void* out, const void* const* updates, int K) {
+// The argument checks of the sort entry points (fa_trimmed_mean, fa_median_window_mean, fa_order_mean_wide),
+// reported in `who`'s name, in two halves: the entry point's own bound on its count (trim, keep) is refused
+// between them, after a bad K and before a bad P, as it always was. `cap`: the clients the entry point takes.
+int check_sort_ptrs(const char* who, const void* out, const void* const* updates, int K, int cap = kMaxK) {
     if (!out || !updates) return fail(FA_EINVAL, "%s: null pointer argument", who);
-    if (K < 1 || K > kMaxK) return fail(FA_EINVAL, "%s: K=%d outside 1..%d", who, K, kMaxK);
+    if (K < 1 || K > cap) return fail(FA_EINVAL, "%s: K=%d outside 1..%d", who, K, cap);
     return FA_OK;
 }
 

@@ -278,6 +278,47 @@ def median(out, updates, stream=None):
     return trimmed_mean(out, updates, median_trim(len(updates)), stream)
 
 
+MAX_WIDE_ORDER_K = 1024     # clients of one fa_order_mean_wide call (a wavefront sorts a coordinate: 16 keys a lane)
+
+
+def trimmed_mean_wide(out, updates, trim, stream=None):
+    """:func:`trimmed_mean` for 1 <= K <= 1024 updates (``fa_order_mean_wide``, kernel ``k_order_wide``;
+    DESIGN.md §3.14): the same rule and the same bits, one pass that reads every update once. Always the wide
+    kernel, also at K <= 64. The call's client table (``fa_order_mean_wide_work(K)`` bytes) is a device tensor
+    allocated on the launching stream."""
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_WIDE_ORDER_K:
+        raise ValueError(f"trimmed_mean_wide takes 1..{MAX_WIDE_ORDER_K} updates, got {K}")
+    P = out.numel()
+    dev = out.device
+    _check_dev("out", out, P, None)
+    upd_dt = updates[0].dtype
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one trimmed_mean_wide call must share a dtype")
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):           # (scratch belongs to the stream that launches: DESIGN.md §3.7)
+            work = torch.empty(int(lib.fa_order_mean_wide_work(K)), dtype=torch.uint8, device=dev)
+        rc = lib.fa_order_mean_wide(out.data_ptr(), fa_dtype(out), _abi.ptr_array([u.data_ptr() for u in updates]),
+                                    fa_dtype(upd_dt), K, int(trim), P, work.data_ptr(), ctypes_stream(s))
+    _abi.check(rc)
+    return out
+
+
+def order_wide_tile(dtype, K):
+    """The consecutive coordinates one workgroup of ``k_order_wide`` takes for K updates of ``dtype``
+    (``fa_order_mean_wide_tile``): tools and tests place sizes at the tile's edges with it."""
+    return int(_abi.load().fa_order_mean_wide_tile(fa_dtype(dtype), int(K)))
+
+
+def median_wide(out, updates, stream=None):
+    """Coordinate-wise median of 1 <= K <= 1024 updates: :func:`trimmed_mean_wide` with ``trim = (K - 1) // 2``."""
+    return trimmed_mean_wide(out, updates, median_trim(len(updates)), stream)
+
+
 _SQDIST_F32 = (torch.float32, torch.float16, torch.bfloat16)
 _SQDIST_F64 = (torch.float64, torch.int32, torch.int64)
 

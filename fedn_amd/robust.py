@@ -50,7 +50,10 @@ All rules are UNWEIGHTED: ``num_examples`` plays no part. One device only. A rou
 ``ops.MAX_ORDER_K`` (64) updates — one launch's table, one sorting network, one K x K matrix — except the
 two clipping rules, ``centered_clip`` and ``dp_clipped_mean``, which take ``ops.MAX_CLIP_K`` (1024): past 64
 their step is a chain of ``fa_clip_fold`` launches over chunks of 64 clients that carries the accumulator in
-the compute type (kernel ``k_clip_fold``), the same definition bit for bit.
+the compute type (kernel ``k_clip_fold``), the same definition bit for bit; and except
+``result_wide``, the trimmed mean and median of up to ``ops.MAX_WIDE_ORDER_K`` (1024) updates, where a
+wavefront instead of a lane sorts a coordinate (``fa_order_mean_wide``, kernel ``k_order_wide``; DESIGN.md
+§3.14).
 
 Stream ordering (the rules DESIGN.md records for fresh HBM, §3.7): a buffer is allocated on the
 stream that first writes it (staged updates and the ring on the copy stream, results on the compute
@@ -340,6 +343,20 @@ class RobustPipeline:
         if trim < 0 or 2 * trim >= K:
             raise ValueError(f"trim={trim} leaves nothing of {K} updates")
         return self._round(lambda: {dt: self._reduce_group(dt, trim) for dt in self.layout.groups})
+
+    def result_wide(self, trim):
+        """:meth:`result` for a round of up to ``ops.MAX_WIDE_ORDER_K`` (1024) updates. Up to
+        ``ops.MAX_ORDER_K`` it IS :meth:`result`: the register network's kernel, bits and speed. Past that every
+        dtype group is one ``ops.trimmed_mean_wide`` launch over all K updates (kernel ``k_order_wide``), or one
+        launch a slice where updates sit on the host: the slices shrink with the number of host-side updates, so
+        the ring never exceeds :meth:`result`'s worst case of 2 x 64 x ``SLICE_BYTES``. Coordinates are
+        independent: the same bits wherever the updates sit."""
+        K = self._clients(ops.MAX_WIDE_ORDER_K)
+        if K <= ops.MAX_ORDER_K:
+            return self.result(trim)
+        if trim < 0 or 2 * trim >= K:
+            raise ValueError(f"trim={trim} leaves nothing of {K} updates")
+        return self._round(lambda: {dt: self._reduce_group(dt, trim, wide=True) for dt in self.layout.groups})
 
     def select_mean(self, f, m):
         """Krum (``m = 1``) / Multi-Krum (``m = K - f``): the unweighted mean of the ``m`` updates that
@@ -766,10 +783,12 @@ class RobustPipeline:
         return [(np.ascontiguousarray(arrays[i]).reshape(-1), off) for i, off in self.layout.members[dt]
                 if self.layout.sizes[i]]
 
-    def _reduce_group(self, dt, trim, subset=None, keep=None):
+    def _reduce_group(self, dt, trim, subset=None, keep=None, wide=False):
         """Group ``dt`` of the trimmed mean over the held updates — all of them, or those at the FIFO
         indices ``subset`` — as a pinned host tensor. With ``keep`` the rule is the mean of the ``keep``
-        values closest to the median instead (``ops.median_window_mean``; ``trim`` plays no part)."""
+        values closest to the median instead (``ops.median_window_mean``; ``trim`` plays no part). ``wide``:
+        ``ops.trimmed_mean_wide`` over all the updates, more than ``ops.MAX_ORDER_K`` of them, with the ring's
+        slices cut so that it holds no more than 64 full slices a buffer."""
         n = self.layout.group_elems[dt]
         odt = self._out_dt[dt]
         host = torch.empty(n, dtype=odt, pin_memory=True)
@@ -780,7 +799,9 @@ class RobustPipeline:
         def launch(b, lo, hi, views, step):
             if b not in outs:
                 outs[b] = torch.empty(step, dtype=odt, device=self.device)
-            if keep is None:
+            if wide:
+                ops.trimmed_mean_wide(outs[b][:hi - lo], views, trim, stream=self.compute)
+            elif keep is None:
                 ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)
             else:
                 ops.median_window_mean(outs[b][:hi - lo], views, keep, stream=self.compute)
@@ -790,14 +811,19 @@ class RobustPipeline:
             # launch that reuses outs[b]
             host[lo:hi].copy_(outs[b][:hi - lo], non_blocking=True)
 
-        self._walk_group(dt, subset, launch, after)
+        slice_bytes = None
+        if wide:
+            on_host = sum(1 for u in self.updates if not isinstance(u, StagedModel))
+            slice_bytes = SLICE_BYTES * ops.MAX_ORDER_K // max(on_host, ops.MAX_ORDER_K)
+        self._walk_group(dt, subset, launch, after, slice_bytes=slice_bytes)
         return host
 
-    def _walk_group(self, dt, subset, launch, after, sliced=False):
+    def _walk_group(self, dt, subset, launch, after, sliced=False, slice_bytes=None):
         """Run ``launch(b, lo, hi, views, step)`` over group ``dt`` of the updates at ``subset`` (all when
         None): once when they all sit in HBM, else slice by slice with the host-side ones copied through
         the two-buffer ring; ``after(b, lo, hi)`` follows each launch's timing events. ``sliced`` walks
         the slice bounds even when every update sits in HBM (no ring then: the views are the updates' own).
+        ``slice_bytes``: bytes of one update's slice, ``SLICE_BYTES`` when None.
 
         Every view handed to ``launch`` starts on a 16-byte boundary, so the kernels take their 16-byte
         load paths: a staged update's group starts at a multiple of ``layout.ALIGN`` bytes, slices
@@ -808,7 +834,7 @@ class RobustPipeline:
         used = list(range(len(self.updates))) if subset is None else list(subset)
         on_host = [k for k in used if not isinstance(self.updates[k], StagedModel)]
         if on_host or sliced:
-            step = max(SLICE_ALIGN, SLICE_BYTES // isz // SLICE_ALIGN * SLICE_ALIGN)
+            step = max(SLICE_ALIGN, (SLICE_BYTES if slice_bytes is None else slice_bytes) // isz // SLICE_ALIGN * SLICE_ALIGN)
         else:
             step = n                                 # every update in HBM: one launch
         step = min(step, n)

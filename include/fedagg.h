@@ -32,13 +32,14 @@
 #ifndef FEDAGG_H
 #define FEDAGG_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 15
+#define FA_ABI_VERSION 16
 
 /* element type codes */
 enum fa_dtype {
@@ -567,6 +568,30 @@ int fa_gaussian_noise(void* out, const void* x, int dtype, double sigma, uint64_
  */
 int fa_clip_fold(void* out, int out_dtype, void* carry_out, const void* carry_in, const void* center,
                  const void* const* updates, int upd_dtype, const double* coef, int K, int64_t P, void* stream);
+
+/*
+ * fa_order_mean_wide (ABI 16): fa_trimmed_mean's rule — the same total order, the same ascending sum from
+ * s[trim], one division, one rounding, the same (upd, out) pairs, bit for bit — for 1 <= K <= 1024 client
+ * updates in ONE pass that reads every update once. A wavefront sorts a coordinate's keys (KP / 64 a lane, KP the
+ * power of two from 128 with K <= KP) by a bitonic merge on registers and wavefront shuffles, a workgroup a tile
+ * of coordinates staged through LDS. It always runs this kernel, also at K <= 64.
+ *
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype. The array is read before the call
+ *          returns: the pointers travel to `work` in kernel arguments, in stream order.
+ * work     DEVICE buffer of fa_order_mean_wide_work(K) bytes, 8-byte aligned: the call's client table. It
+ *          belongs to the call until the stream has run it.
+ * fa_order_mean_wide_work: 0 for K outside 1..1024. fa_order_mean_wide_tile: the consecutive coordinates one
+ * workgroup takes for K updates of upd_dtype (8 .. 64; the last tile of a buffer may be shorter), 0 for a K or
+ * dtype the entry point refuses — for tools and tests that place sizes at the tile's edges.
+ * FA_EINVAL: a null out, updates or work, K outside 1..1024, trim < 0 or 2*trim >= K, P < 0, a null entry
+ * of updates when P > 0, P past 2^31 - 1 tiles; FA_EDTYPE: any other dtype pair; FA_OK for P = 0 with no
+ * launch — all before any HIP call. FA_EHIP where the device gives a workgroup less LDS than the tile takes
+ * (up to 129 KiB; gfx950 has 160). fa_last_kernel reports "k_order_wide".
+ */
+size_t fa_order_mean_wide_work(int K);
+int fa_order_mean_wide_tile(int upd_dtype, int K);
+int fa_order_mean_wide(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int trim,
+                       int64_t P, void* work, void* stream);
 
 #ifdef __cplusplus
 }
