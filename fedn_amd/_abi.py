@@ -147,6 +147,11 @@ EXPORTS = {
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
         ctypes.c_int, ctypes.c_int, ctypes.c_int64,          # K, trim, P
         ctypes.c_void_p, ctypes.c_void_p]),                  # work, stream
+    "fa_median_window_mean_wide": (ctypes.c_int, [
+        ctypes.c_void_p, ctypes.c_int,                       # out, out_dtype
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,       # updates, upd_dtype
+        ctypes.c_int, ctypes.c_int, ctypes.c_int64,          # K, keep, P
+        ctypes.c_void_p, ctypes.c_void_p]),                  # work, stream
 }
 # measurement / tuning entry points: libfedagg_probe.so only (include/fedagg_probe.h)
 PROBE_EXPORTS = {
@@ -170,7 +175,7 @@ PROBE_EXPORTS = {
         ctypes.POINTER(ctypes.c_int)]),                                    # tile, chain, grid, tiles per flush
 }
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 PAIR_CHAIN_TERMS = 1024  # FA_PAIR_CHAIN_TERMS: R of fa_pairwise_sqdist
 IPC_HANDLE_BYTES = 64    # FA_IPC_HANDLE_BYTES
 RELEASE_WORDS = 8        # FA_RELEASE_WORDS; enum fa_release_word:

@@ -92,6 +92,7 @@ size_t dt_size(int dt) {
 #include "order_mean.h"       // coordinate-wise trimmed mean / median (k_order_mean, fa_trimmed_mean)
 #include "order_wide.h"       // the same rule for up to 1024 clients, a wavefront a coordinate (k_order_wide, fa_order_mean_wide)
 #include "median_window.h"    // mean of the values closest to the median, Bulyan (k_median_window, fa_median_window_mean)
+#include "window_wide.h"      // the same rule for up to 1024 clients, mean around median (k_window_wide, fa_median_window_mean_wide)
 #include "pair_dist.h"        // pairwise squared distances for Krum / Multi-Krum (k_pair_sqdist, fa_pairwise_sqdist)
 #include "wmean_dist.h"       // weighted mean and the K squared distances to it (k_wmean_dist, fa_weighted_mean_sqdist)
 #include "cclip.h"            // one centred-clipping step and the K squared distances to it (k_cclip_dist, fa_centered_clip_step)
@@ -748,6 +749,20 @@ int fa_median_window_mean(void* out, int out_dtype, const void* const* updates, 
     if (const int rc = check_updates("fa_median_window_mean", updates, K)) return rc;
     return for_dtype(upd_dtype,
                      [&](auto t) { return launch_median_window<decltype(t)>(out, updates, K, keep, P, st); });
+}
+
+int fa_median_window_mean_wide(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int keep,
+                               int64_t P, void* work, void* stream) {
+    g_err[0] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (const int rc = check_sort_ptrs("fa_median_window_mean_wide", out, updates, K, kMaxWideK)) return rc;
+    if (!work) return fail(FA_EINVAL, "fa_median_window_mean_wide: work is NULL");
+    if (keep < 1 || keep > K) return fail(FA_EINVAL, "fa_median_window_mean_wide: keep=%d outside 1..K=%d", keep, K);
+    if (const int rc = check_sort_size("fa_median_window_mean_wide", out_dtype, upd_dtype, P)) return rc;
+    if (P == 0) return FA_OK;
+    if (const int rc = check_updates("fa_median_window_mean_wide", updates, K)) return rc;
+    return for_dtype(upd_dtype,
+                     [&](auto t) { return launch_window_wide<decltype(t)>(out, updates, K, keep, P, work, st); });
 }
 
 int64_t fa_pairwise_sqdist_work(int K, int64_t P) {

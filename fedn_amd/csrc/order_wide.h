@@ -228,37 +228,41 @@ auto for_wide_kp(int K, F&& f) {
 }
 
 // The device's LDS limit for one workgroup, and the kernel's dynamic-LDS attribute raised to `bytes`
-// (needed past 64 KiB). Asked at every launch: the process may drive several devices.
+// (needed past 64 KiB). Asked at every launch: the process may drive several devices. Reported in `who`'s name.
 template <typename KERNEL>
-int wide_raise_lds(KERNEL kernel, size_t bytes) {
+int wide_raise_lds(const char* who, KERNEL kernel, size_t bytes) {
     int dev = 0, limit = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        return fail(FA_EHIP, "fa_order_mean_wide: LDS limit query: %s", hipGetErrorString(e));
+        return fail(FA_EHIP, "%s: LDS limit query: %s", who, hipGetErrorString(e));
     }
     if ((size_t)limit < bytes)
-        return fail(FA_EHIP, "fa_order_mean_wide: the tile needs %zu bytes of LDS, the device gives a workgroup %d", bytes,
-                    limit);
+        return fail(FA_EHIP, "%s: the tile needs %zu bytes of LDS, the device gives a workgroup %d", who, bytes, limit);
     if (bytes > (64u << 10)) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return fail(FA_EHIP, "fa_order_mean_wide: raising the dynamic LDS limit to %zu: %s", bytes, hipGetErrorString(e));
+            return fail(FA_EHIP, "%s: raising the dynamic LDS limit to %zu: %s", who, bytes, hipGetErrorString(e));
         }
     }
     return FA_OK;
 }
 
-template <typename T>
-int launch_order_wide(void* out, const void* const* ups, int K, int trim, int64_t P, void* work, hipStream_t st) {
+// The launch path of the two wide kernels, k_order_wide and window_wide.h's k_window_wide, reported in the entry
+// point `who`'s name: the bound on P, the LDS limit, the client table written to `work` in stream order, the
+// padded client count KP. pick(kp) gives the <T, KP> instantiation (kp a std::integral_constant tag), `name`
+// what fa_last_kernel reports, `count` the rule's own argument (trim or keep).
+template <typename T, typename PICK>
+int launch_wide_kernel(const char* who, const char* name, void* out, const void* const* ups, int K, int count, int64_t P,
+                       void* work, hipStream_t st, PICK&& pick) {
     return for_wide_kp(K, [&](auto kp) -> int {
         using G = WideGeom<T, decltype(kp)::value>;
         // grid = ceil(P / C) workgroups must fit the 32-bit grid dimension
-        if (P > (int64_t)0x7FFFFFFF * G::C) return fail(FA_EINVAL, "fa_order_mean_wide: P=%lld is too large", (long long)P);
-        auto kernel = k_order_wide<T, decltype(kp)::value>;
-        if (const int rc = wide_raise_lds(kernel, G::LDS)) return rc;
+        if (P > (int64_t)0x7FFFFFFF * G::C) return fail(FA_EINVAL, "%s: P=%lld is too large", who, (long long)P);
+        auto kernel = pick(kp);
+        if (const int rc = wide_raise_lds(who, kernel, G::LDS)) return rc;
         const void** tab = static_cast<const void**>(work);
         bool vec = true;
         for (int k0 = 0; k0 < K; k0 += kWideFill) {
@@ -270,9 +274,17 @@ int launch_order_wide(void* out, const void* const* ups, int K, int trim, int64_
             }
             hipLaunchKernelGGL(k_fill_ptrs, dim3(1), dim3(kWideFill), 0, st, tab + k0, chunk, n);
         }
-        g_kernel = "k_order_wide";
+        g_kernel = name;
         hipLaunchKernelGGL(kernel, dim3((unsigned)((P + G::C - 1) / G::C)), dim3(kBlock), G::LDS, st,
-                           static_cast<typename OrderTraits<T>::O*>(out), tab, K, trim, P, (int)vec);
-        return check_launch("fa_order_mean_wide: kernel launch");
+                           static_cast<typename OrderTraits<T>::O*>(out), tab, K, count, P, (int)vec);
+        char what[64];
+        std::snprintf(what, sizeof(what), "%s: kernel launch", who);
+        return check_launch(what);
     });
+}
+
+template <typename T>
+int launch_order_wide(void* out, const void* const* ups, int K, int trim, int64_t P, void* work, hipStream_t st) {
+    return launch_wide_kernel<T>("fa_order_mean_wide", "k_order_wide", out, ups, K, trim, P, work, st,
+                                 [](auto kp) { return k_order_wide<T, decltype(kp)::value>; });
 }

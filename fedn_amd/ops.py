@@ -319,6 +319,33 @@ def median_wide(out, updates, stream=None):
     return trimmed_mean_wide(out, updates, median_trim(len(updates)), stream)
 
 
+def median_window_mean_wide(out, updates, keep, stream=None):
+    """:func:`median_window_mean` for 1 <= K <= 1024 updates (``fa_median_window_mean_wide``, kernel
+    ``k_window_wide``): the same rule and the same bits, one pass that reads every update once.
+    Always the wide kernel, also at K <= 64. The client table is :func:`trimmed_mean_wide`'s."""
+    lib = _abi.load()
+    K = len(updates)
+    if not 1 <= K <= MAX_WIDE_ORDER_K:
+        raise ValueError(f"median_window_mean_wide takes 1..{MAX_WIDE_ORDER_K} updates, got {K}")
+    P = out.numel()
+    dev = out.device
+    _check_dev("out", out, P, None)
+    upd_dt = updates[0].dtype
+    for i, u in enumerate(updates):
+        _check_dev(f"updates[{i}]", u, P, dev)
+        if u.dtype != upd_dt:
+            raise TypeError("all updates in one median_window_mean_wide call must share a dtype")
+    with _on(dev):
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):           # (scratch belongs to the stream that launches: DESIGN.md §3.7)
+            work = torch.empty(int(lib.fa_order_mean_wide_work(K)), dtype=torch.uint8, device=dev)
+        rc = lib.fa_median_window_mean_wide(out.data_ptr(), fa_dtype(out),
+                                            _abi.ptr_array([u.data_ptr() for u in updates]), fa_dtype(upd_dt), K,
+                                            int(keep), P, work.data_ptr(), ctypes_stream(s))
+    _abi.check(rc)
+    return out
+
+
 _SQDIST_F32 = (torch.float32, torch.float16, torch.bfloat16)
 _SQDIST_F64 = (torch.float64, torch.int32, torch.int64)
 

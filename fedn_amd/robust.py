@@ -53,7 +53,8 @@ their step is a chain of ``fa_clip_fold`` launches over chunks of 64 clients tha
 the compute type (kernel ``k_clip_fold``), the same definition bit for bit; and except
 ``result_wide``, the trimmed mean and median of up to ``ops.MAX_WIDE_ORDER_K`` (1024) updates, where a
 wavefront instead of a lane sorts a coordinate (``fa_order_mean_wide``, kernel ``k_order_wide``; DESIGN.md
-§3.14).
+§3.14), and ``mean_around_median``, Bulyan's second stage as a rule of its own over the same range
+(``fa_median_window_mean_wide``, kernel ``k_window_wide``).
 
 Stream ordering (the rules DESIGN.md records for fresh HBM, §3.7): a buffer is allocated on the
 stream that first writes it (staged updates and the ring on the copy stream, results on the compute
@@ -88,6 +89,12 @@ def trim_count(trim_fraction, K):
     """Values dropped at EACH end of K sorted values: ``floor(trim_fraction * K)``, never more than
     ``(K - 1) // 2`` (at least one value is kept whatever the product's rounding does)."""
     return max(0, min(math.floor(trim_fraction * K), (K - 1) // 2))
+
+
+def meamed_keep(byzantine_fraction, K):
+    """Values mean-around-median keeps of K: all but ``floor(byzantine_fraction * K)``, never fewer than the
+    ``K - (K - 1) // 2`` a majority of honest clients leaves."""
+    return K - max(0, min(math.floor(byzantine_fraction * K), (K - 1) // 2))
 
 
 def krum_f(byzantine_fraction, K):
@@ -357,6 +364,19 @@ class RobustPipeline:
         if trim < 0 or 2 * trim >= K:
             raise ValueError(f"trim={trim} leaves nothing of {K} updates")
         return self._round(lambda: {dt: self._reduce_group(dt, trim, wide=True) for dt in self.layout.groups})
+
+    def mean_around_median(self, keep):
+        """Mean around median (Xie, Koyejo and Gupta, 2018) of a round of up to
+        ``ops.MAX_WIDE_ORDER_K`` (1024) updates: per element the mean of the ``keep`` sorted values closest to
+        the median, :meth:`bulyan`'s second stage over every held update. Host arrays like :meth:`result`'s. Up
+        to ``ops.MAX_ORDER_K`` updates the register network's kernel (``ops.median_window_mean``), past that
+        ``ops.median_window_mean_wide`` (kernel ``k_window_wide``) through :meth:`result_wide`'s walk: one
+        launch a dtype group, or one a shrunk slice where updates sit on the host. The same bits either way."""
+        K = self._clients(ops.MAX_WIDE_ORDER_K)
+        if not 1 <= keep <= K:
+            raise ValueError(f"keep={keep} outside 1..{K} updates")
+        wide = K > ops.MAX_ORDER_K
+        return self._round(lambda: {dt: self._reduce_group(dt, 0, keep=keep, wide=wide) for dt in self.layout.groups})
 
     def select_mean(self, f, m):
         """Krum (``m = 1``) / Multi-Krum (``m = K - f``): the unweighted mean of the ``m`` updates that
@@ -787,8 +807,9 @@ class RobustPipeline:
         """Group ``dt`` of the trimmed mean over the held updates — all of them, or those at the FIFO
         indices ``subset`` — as a pinned host tensor. With ``keep`` the rule is the mean of the ``keep``
         values closest to the median instead (``ops.median_window_mean``; ``trim`` plays no part). ``wide``:
-        ``ops.trimmed_mean_wide`` over all the updates, more than ``ops.MAX_ORDER_K`` of them, with the ring's
-        slices cut so that it holds no more than 64 full slices a buffer."""
+        ``ops.trimmed_mean_wide`` (with ``keep``: ``ops.median_window_mean_wide``) over all the updates, more
+        than ``ops.MAX_ORDER_K`` of them, with the ring's slices cut so that it holds no more than 64 full slices
+        a buffer."""
         n = self.layout.group_elems[dt]
         odt = self._out_dt[dt]
         host = torch.empty(n, dtype=odt, pin_memory=True)
@@ -799,7 +820,9 @@ class RobustPipeline:
         def launch(b, lo, hi, views, step):
             if b not in outs:
                 outs[b] = torch.empty(step, dtype=odt, device=self.device)
-            if wide:
+            if wide and keep is not None:
+                ops.median_window_mean_wide(outs[b][:hi - lo], views, keep, stream=self.compute)
+            elif wide:
                 ops.trimmed_mean_wide(outs[b][:hi - lo], views, trim, stream=self.compute)
             elif keep is None:
                 ops.trimmed_mean(outs[b][:hi - lo], views, trim, stream=self.compute)

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define FA_ABI_VERSION 16
+#define FA_ABI_VERSION 17
 
 /* element type codes */
 enum fa_dtype {
@@ -592,6 +592,26 @@ size_t fa_order_mean_wide_work(int K);
 int fa_order_mean_wide_tile(int upd_dtype, int K);
 int fa_order_mean_wide(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int trim,
                        int64_t P, void* work, void* stream);
+
+/*
+ * fa_median_window_mean_wide (ABI 17): fa_median_window_mean's rule — the same sort, med kept in A, the same
+ * window start, the same ascending sum from s[a], one division, one rounding, the same (upd, out) pairs, bit for
+ * bit — for 1 <= K <= 1024 client updates in ONE pass that reads every update once: "mean around median" (Xie,
+ * Koyejo and Gupta, 2018) of a whole cohort. The tile, the load and the wavefront's sort are fa_order_mean_wide's;
+ * the wavefront that sorted a coordinate then counts its window start with a ballot, and one lane a coordinate sums
+ * the window (kernel k_window_wide). It always runs this kernel, also at K <= 64.
+ *
+ * updates  HOST array of K DEVICE pointers, each P elements of upd_dtype, read before the call returns
+ * keep     the window length, 1 <= keep <= K
+ * work     DEVICE buffer of fa_order_mean_wide_work(K) bytes, 8-byte aligned: the call's client table. It
+ *          belongs to the call until the stream has run it. fa_order_mean_wide_tile gives this kernel's tile too.
+ * FA_EINVAL: a null out, updates or work, K outside 1..1024, keep outside 1..K, P < 0, a null entry of updates
+ * when P > 0, P past 2^31 - 1 tiles; FA_EDTYPE: any other dtype pair; FA_OK for P = 0 with no launch — all
+ * before any HIP call. FA_EHIP where the device gives a workgroup less LDS than the tile takes.
+ * fa_last_kernel reports "k_window_wide".
+ */
+int fa_median_window_mean_wide(void* out, int out_dtype, const void* const* updates, int upd_dtype, int K, int keep,
+                               int64_t P, void* work, void* stream);
 
 #ifdef __cplusplus
 }
